@@ -1,6 +1,13 @@
 """Throughput benchmark: env-steps/s of the batched MAGICAL hot path on MI355X.
 
 python bench.py --gpus N --steps K --warmup W [--envs 4096] [--env MoveToRegion-Demo-LoRes4E-v0]
+                [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (its per-kernel and roofline
+figures are the timed launches' own HIP-event averages).  --full adds what takes runs of its own: the CPU
+baseline (--no-cpu-baseline drops it again) and, for chunked runs, the isolated pass behind the per-kernel
+roofline times.  --dump-outputs DIR writes what the last timed step returned (observations, reward, done,
+eval_score) as DIR/<name>.npy, see dump_outputs().
 
 One env-step = one step() of every env: action decode, 10 physics substeps
 (Chipmunk-7 semantics), episode bookkeeping + score, the in-place reset of the
@@ -270,6 +277,43 @@ def kernel_record(name, ms, preproc, n, pmc, frames_only=False, window=False, st
             "valu_issue_frac": pmc and pmc.get("valu_issue_frac"), "wait_any_frac": pmc and pmc.get("wait_any_frac")}
 
 
+DUMP_BUDGET = 48 << 20      # --dump-outputs: bytes of the sampled observation rows at most (64 MB in all)
+
+
+def dump_outputs(path, obs, reward, done, info):
+    """--dump-outputs: what the last timed step returned, as <path>/<name>.npy in float32 (float64 tensors, i.e.
+    eval_score, stay float64).  reward, done and info's tensors are written for every env.  The observations of
+    every env would be GBs, so <obs key>.npy holds the rows of a fixed sample of envs (numpy RandomState(0): the
+    same envs in every run with the same arguments, as many as fit DUMP_BUDGET) and <obs key>_rowsum.npy every
+    env's sum over its whole observation (float64, exact for the uint8 frames), so that a difference in any env
+    shows.  Under the multi-GPU gather the [W, n, ...] results are written as W x n rows.  Returns the record
+    for the result line."""
+    import numpy as np
+    import torch
+    lead = reward.dim()   # 1, or 2 under the gather
+
+    def rows_of(t):
+        return t.reshape((-1,) + tuple(t.shape[lead:]))
+
+    def save(name, t):
+        t = t if t.dtype == torch.float64 else t.to(torch.float32)
+        np.save(os.path.join(path, f"{name}.npy"), t.contiguous().cpu().numpy())
+
+    os.makedirs(path, exist_ok=True)
+    rows = reward.numel()
+    arrays = [(k, rows_of(v)) for k, v in obs.items()]
+    per_env = sum(4 * v[0].numel() for _, v in arrays)
+    k = max(1, min(rows, DUMP_BUDGET // per_env))
+    idx = torch.as_tensor(np.sort(np.random.RandomState(0).choice(rows, k, replace=False)), device=reward.device)
+    for name, v in arrays:
+        save(name, v.index_select(0, idx))
+        if k < rows:
+            save(f"{name}_rowsum", v.reshape(rows, -1).sum(dim=1, dtype=torch.float64))
+    for name, v in [("reward", reward), ("done", done)] + sorted(info.items()):
+        save(name, rows_of(v))
+    return {"dir": path, "envs": rows, "observation_rows_sampled": k, "sample": "numpy RandomState(0), sorted"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -280,6 +324,11 @@ def main():
     ap.add_argument("--cpu-workers", type=int, default=0, help="0: every CPU this job may use")
     ap.add_argument("--cpu-steps", type=int, default=1500)  # ~1-2 s of CPU work per process
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline and, for chunked runs, the isolated "
+                         "pass for the per-kernel roofline times (--iso-steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's results as DIR/<name>.npy")
     ap.add_argument("--gather", dest="gather", action="store_true", default=None,
                     help="all-gather every step's results to every rank (default for N > 1)")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
@@ -306,11 +355,12 @@ def main():
                     help="frames-mode receivers: window ring views (mg_restack_window) or materialised stacks "
                          "(mg_restack)")
     args = ap.parse_args()
+    want_cpu = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the CPU baseline is measured here, in the launcher parent, before any rank (or GPU) exists; rank 0
         # puts it on its line
-        if not args.no_cpu_baseline:
+        if want_cpu:
             os.environ[CPU_ENV] = json.dumps(measure_cpu_baseline(args))
         sys.exit(launch_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -323,7 +373,7 @@ def main():
     # before this process touches a GPU (an outside torch.distributed.run: the other ranks wait in the
     # process-group rendezvous meanwhile)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and want_cpu:
         cpu = json.loads(os.environ[CPU_ENV]) if os.environ.get(CPU_ENV) else measure_cpu_baseline(args)
         cpu["measured_in"] = "launcher parent" if os.environ.get(CPU_ENV) else "rank 0 before GPU init"
 
@@ -409,9 +459,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
+    last = None
     for s in range(args.steps):
         vec.random_actions(args.warmup + s, out=actions)
-        step(actions)
+        last = step(actions)
     if gather:   # the timed region ends after the last step's exchange (all-gather + restack)
         shard.wait_all()
     if chunks > 1:   # ... and after every chunk's last step
@@ -420,6 +471,9 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:   # before anything below steps a simulator again
+        dumped = dump_outputs(args.dump_outputs, *(last.results() if gather else last))
     import ctypes
     if chunks > 1:   # per-launch averages over the chunks' launches (each launch covers n / chunks envs)
         tms = vec.read_timing()
@@ -436,7 +490,8 @@ def main():
     live = float(sim0.bodies()[1][:, 3].double().mean().item())   # active arbiters per env after the timed run
     step_bytes = step_state_bytes(form, caps, live)
     # chunked runs: the timed launches overlap the other chunk's kernels, so their HIP-event times are
-    # co-running figures.  The roofline's per-kernel times come from an isolated pass after the timed region:
+    # co-running figures.  Under --full the roofline's per-kernel times come from an isolated pass after the timed
+    # region (a plain run reports the co-running figures and labels them so):
     # chunk 0 stepped alone (its step, reset and render kernels back to back on one stream, nothing beside
     # them), args.iso_steps steps of the same env count per launch.  Unchunked runs keep the timed launches (one
     # stream; the many-block scenes' next-layout shadow co-runs on the simulator's side stream in every step, as
@@ -445,7 +500,7 @@ def main():
     # under rocprofv3 the same HIP events read 2.47 / 2.58 ms against rocprof's 2.45 / 2.54 ms -- the events
     # agree with the profiler within the same run, and the profiler itself shortens that kernel by ~10%.
     iso = None
-    if chunks > 1 and args.iso_steps > 0:
+    if args.full and chunks > 1 and args.iso_steps > 0:
         native.check(lib.mg_enable_timing(sim0.handle, args.iso_steps))
         a0 = torch.empty(sim0.num_envs, dtype=torch.uint8, device=device)
         for s in range(args.iso_steps):
@@ -476,7 +531,7 @@ def main():
     if rank == 0:
         frames_only = gather and args.gather_mode == "frames"
         stacks_window = bool(getattr(vec, "window_k", 0)) and not gather
-        # per-kernel roofline records: from the isolated pass when the timed launches co-ran (chunks > 1)
+        # per-kernel roofline records: from the isolated pass (--full) when the timed launches co-ran (chunks > 1)
         k_step, k_render, k_reset = (iso["step_kernel"], iso["render_kernel"], iso["reset_kernel"]) if iso else \
             (t_step_ms, t_render_ms, t_reset_ms)
         kernels = {
@@ -485,7 +540,9 @@ def main():
             "step_kernel": kernel_record("step_kernel", k_step, spec.preproc, units, pmc_for("step_kernel"),
                                          step_bytes=step_bytes),
             "reset_kernel": {"ms": round(k_reset, 4)},
-            "timing": "isolated (chunk 0 alone after the timed region)" if iso else "timed launches (one stream)",
+            "timing": "isolated (chunk 0 alone after the timed region)" if iso else
+                      "timed launches (co-running: chunks overlap; --full isolates them)" if chunks > 1 else
+                      "timed launches (one stream)",
             "step_form": {"form": form, "envs_per_workgroup": blk, "caps_bodies_shapes_constraints_arbiters": caps,
                           "live_arbiters_per_env": round(live, 3), "state_bytes_per_env_step": step_bytes},
         }
@@ -564,6 +621,8 @@ def main():
                         "exchange_ms_per_step": round(exchange_ms, 4) if exchange_ms is not None else None}
                        if gather else None),
             "cpu_baseline": cpu,
+            "full": args.full,
+            "outputs_dumped": dumped,
         }
         print(json.dumps(out), flush=True)
     (shard if gather else vec).close()

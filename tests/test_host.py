@@ -460,7 +460,7 @@ def test_bench_launches_ranks_itself():
     the N > 1 gather default is on."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--full",
                           "--cpu-steps", "60", "--cpu-workers", "2"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -515,6 +515,64 @@ def test_bench_byte_models():
         assert bench.env_overrides().get("MG_STEP_VARIANT") == "4"
     finally:
         del os.environ["MG_STEP_VARIANT"]
+
+
+def test_bench_plain_run_measures_no_cpu_baseline():
+    """Without --full the CPU baseline is not measured (--dry-run: the launcher path of one rank, no GPU)."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run"],
+                         capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["ranks_seen"] == 1 and line["cpu_baseline"] is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every tensor of a step's results lands as float32 / float64 .npy; observations too
+    large for the budget are cut to a fixed sample of env rows (the same in every call) plus every env's exact sum;
+    gathered [W, n, ...] results are written as W x n rows."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 7
+    g = torch.Generator().manual_seed(3)
+    obs = {"allo": torch.randint(0, 256, (n, 4, 4, 3), dtype=torch.uint8, generator=g),
+           "past_obs": torch.randint(0, 256, (n, 12, 4, 4), dtype=torch.uint8, generator=g).permute(0, 2, 3, 1)}
+    rew, done = torch.rand(n, generator=g), torch.rand(n, generator=g) < 0.5
+    info = {"eval_score": torch.rand(n, dtype=torch.float64, generator=g)}
+    rec = bench.dump_outputs(str(tmp_path / "a"), obs, rew, done, info)
+    assert rec["envs"] == n and rec["observation_rows_sampled"] == n
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["allo", "done", "eval_score", "past_obs", "reward"]
+    assert all(v.dtype == (np.float64 if k == "eval_score" else np.float32) for k, v in got.items())
+    assert np.array_equal(got["past_obs"], obs["past_obs"].numpy()) and np.array_equal(got["allo"], obs["allo"].numpy())
+    assert np.array_equal(got["reward"], rew.numpy()) and np.array_equal(got["done"], done.numpy())
+    assert np.array_equal(got["eval_score"], info["eval_score"].numpy())
+    # a budget of 3 envs' float32 observations: 3 sampled rows, the same twice, and the row sums of all 7 envs
+    per_env = 4 * (4 * 4 * 3 + 4 * 4 * 12)
+    old, bench.DUMP_BUDGET = bench.DUMP_BUDGET, 3 * per_env + 5
+    try:
+        recs = [bench.dump_outputs(str(tmp_path / d), obs, rew, done, info) for d in ("b", "c")]
+        # gathered results of 2 ranks: [2, n, ...]
+        wide = bench.dump_outputs(str(tmp_path / "w"), {k: torch.stack([v, v]) for k, v in obs.items()},
+                                  torch.stack([rew, rew]), torch.stack([done, done]),
+                                  {"eval_score": torch.stack([info["eval_score"]] * 2)})
+    finally:
+        bench.DUMP_BUDGET = old
+    assert recs[0]["observation_rows_sampled"] == 3 and recs[0] == dict(recs[1], dir=recs[0]["dir"])
+    b, c = (tmp_path / "b"), (tmp_path / "c")
+    assert sorted(os.listdir(b)) == sorted(os.listdir(c)) and "allo_rowsum.npy" in os.listdir(b)
+    for f in os.listdir(b):
+        assert np.array_equal(np.load(b / f), np.load(c / f)), f
+    rows = np.load(b / "past_obs.npy")
+    full = obs["past_obs"].numpy().astype(np.float32)
+    assert rows.shape == (3, 4, 4, 12) and all(any(np.array_equal(r, e) for e in full) for r in rows)
+    assert np.array_equal(np.load(b / "past_obs_rowsum.npy"), full.reshape(n, -1).sum(1, dtype=np.float64))
+    assert np.load(b / "reward.npy").shape == (n,)
+    assert wide["envs"] == 2 * n and np.load(tmp_path / "w" / "reward.npy").shape == (2 * n,)
+    assert np.load(tmp_path / "w" / "allo.npy").shape == (3, 4, 4, 3)
+    assert np.load(tmp_path / "w" / "allo_rowsum.npy").shape == (2 * n,)
 
 
 GATHER_CASES = [("MoveToRegion-Demo-LoRes4E-v0", "frames"), ("MoveToRegion-Demo-LoRes4E-v0", "stacked"),

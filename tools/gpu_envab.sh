@@ -13,7 +13,7 @@ for ENV in "$@"; do
   for SET in $SETS; do
     L="$OUT/bench.$ENV.${SET//[^A-Za-z0-9_.-]/_}.$rep.log"
     if [ "$SET" = "-" ]; then EV=(); else IFS=, read -ra EV <<< "$SET"; fi
-    timeout -k 10 300 env "${EV[@]}" python bench.py --steps 100 --warmup 10 --no-cpu-baseline --env "$ENV" --envs $N > "$L" 2>&1
+    timeout -k 10 300 env "${EV[@]}" python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --env "$ENV" --envs $N > "$L" 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "bench $ENV $SET rc=$rc"; tail -3 "$L"; exit $rc; }
     tail -1 "$L" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$ENV', '$SET', $rep, d['value'], d['ms_per_step'], {k: d['kernels'][k]['ms'] for k in ('step_kernel', 'render_kernel')})"
   done

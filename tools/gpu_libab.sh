@@ -14,7 +14,7 @@ for ENV in "$@"; do
     V=${VA%%:*}; A=""; [ "$V" != "$VA" ] && A=${VA#*:}
     if [ "$V" = "-" ]; then unset MAGICAL_AMD_EXP_LIB; else export MAGICAL_AMD_EXP_LIB=$V; fi
     L="$OUT/bench.$ENV.${VA//[^A-Za-z0-9_.-]/_}.$rep.log"
-    timeout -k 10 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --env "$ENV" --envs $N $A > "$L" 2>&1
+    timeout -k 10 300 python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --env "$ENV" --envs $N $A > "$L" 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "bench $ENV $VA rc=$rc"; tail -3 "$L"; exit $rc; }
     tail -1 "$L" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$ENV', '$VA', $rep, d['value'], d['ms_per_step'], {k: d['kernels'][k]['ms'] for k in ('step_kernel', 'render_kernel')}, d['kernel_ms_per_step'])"
   done

@@ -11,12 +11,12 @@ export PYTHONDONTWRITEBYTECODE=1
 for spec in "MoveToRegion-Demo-LoRes4E-v0 4096" "MoveToCorner-Demo-LoRes4E-v0 4096" "ClusterColour-Demo-LoResStack-v0 8192" "MatchRegions-TestAll-LoRes4E-v0 8192"; do
   set -- $spec
   T="$R/gpurun_out/$TAG/$1"
-  timeout -k 10 400 python bench.py --env $1 --envs $2 --steps 100 --warmup 10 --cpu-steps 600 > $T.log 2>&1 || { echo "FAIL $1"; tail -5 $T.log; exit 1; }
+  timeout -k 10 400 python bench.py --env $1 --envs $2 --steps 100 --warmup 10 --full --cpu-steps 600 > $T.log 2>&1 || { echo "FAIL $1"; tail -5 $T.log; exit 1; }
   tail -1 $T.log > $T.json
   python -c "import json; d=json.load(open('$T.json')); print('$1', d['value'], d['ms_per_step'], {k: d['kernels'][k]['ms'] for k in ('step_kernel', 'render_kernel')}, d['roofline']['frac'], d['roofline']['step_frac'], d['cpu_baseline']['one_core_env_steps_s'], d['cpu_baseline']['value'])"
   EPL=$(python -c "import json; print(json.load(open('$T.json'))['kernel_ms_per_step']['envs_per_launch'])")
   cd /tmp && export TMPDIR=/tmp
-  B="--env $1 --envs $2 --no-cpu-baseline"
+  B="--env $1 --envs $2 --full --no-cpu-baseline"
   timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$T.prof/stats" -o run -- python "$R/bench.py" $B --steps 20 --warmup 5 > /dev/null 2>&1 || { echo "FAIL stats $1"; exit 1; }
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d "$T.prof/fetch" -o run -- python "$R/bench.py" $B --steps 5 --warmup 2 > /dev/null 2>&1 || { echo "FAIL fetch $1"; exit 1; }
   timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d "$T.prof/write" -o run -- python "$R/bench.py" $B --steps 5 --warmup 2 > /dev/null 2>&1 || { echo "FAIL write $1"; exit 1; }
