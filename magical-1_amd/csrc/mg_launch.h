@@ -1,8 +1,10 @@
-// mg_launch.h -- host-side launchers of the device kernels (one translation unit
-// per kernel family: mg_physics.hip, mg_raster.hip; the C ABI lives in mg_sim.hip).
+// mg_launch.h -- host-side launchers of the device kernels (one translation unit per kernel family: mg_reset.hip,
+// mg_step_*.hip with their dispatch in mg_physics.hip, mg_raster.hip; the C ABI lives in mg_sim.hip).  The step
+// kernel's forms, slot caps and LDS view: mg_stepforms.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mg_state.h"
+#include "mg_stepforms.h"
 
 // coop: one env per 64-lane wave (reset_kernel_coop); fused_reset: the step kernel runs the auto-reset of its
 // done envs itself (robot scenes without layout randomisation, mg_step)
@@ -40,29 +42,13 @@ hipError_t mg_launch_seed(const MGState &S, const uint32_t *seeds_dev, hipStream
 // grid-stride range in turn; 0: one wavefront per env
 hipError_t mg_launch_reset(const MGState &S, const mg_library *L, TaskCfg cfg, const uint8_t *mask, hipStream_t st,
                            int max_waves = 0);
-// LDS-resident substeps: per-env slot caps of a task and envs per workgroup
-struct StepCaps { int nb, ns, nc, na, blk, shw; };  // shw: world-space shape scratch per lane in LDS
-size_t mg_step_lds_bytes(const StepCaps &c, int blk);
-// compiled LDS variant matching these caps for n_envs (0: the HBM-state kernel)
-int mg_step_variant(const StepCaps &c, int n_envs);
-// compiled envs-per-workgroup sizes of a variant
-bool mg_step_blk_ok(int variant, int blk);
-// Slot caps of the LDS-resident variants (compile-time, so every LDS address folds to a constant
-// offset from the lane's column): 0 = state stays in HBM.
-__host__ __device__ constexpr StepCaps step_variant_caps(int v) {
-    return v == 1 ? StepCaps{6, 5, 10, 20, 16, 3}    // robot only (MoveToRegion)
-         : v == 2 ? StepCaps{7, 6, 12, 32, 16, 0}    // robot + one single-shape block (MoveToCorner; no LDS left for shapes)
-         : v == 3 ? StepCaps{14, 53, 26, 48, 1, 0}   // up to 8 blocks incl. stars (Cluster*, MatchRegions): runtime lists
-         : v == 4 ? StepCaps{14, 53, 26, 48, 1, 0}   // the same scenes, one env per 64-lane wavefront (cooperative)
-         : StepCaps{0, 0, 0, 0, 0, 0};
-}
-
-// one compiled step-kernel form (defined in mg_stepk.h, instantiated in mg_step_*.hip)
+// one compiled step-kernel form: a (form, envs per workgroup) pair of mg_stepforms.h (defined in mg_stepk.h,
+// instantiated in mg_step_*.hip)
 template <int VAR, int BLK>
 hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, int max_steps, int auto_reset,
                            const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
                            uint8_t *reset_mask, hipStream_t st);
-hipError_t mg_launch_step(const MGState &S, const mg_library *L, TaskCfg cfg, int variant, int blk, int max_steps,
+hipError_t mg_launch_step(const MGState &S, const mg_library *L, TaskCfg cfg, int form, int blk, int max_steps,
                           int auto_reset, const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
                           uint8_t *reset_mask, hipStream_t st);
 hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderOut &ro, int mode, hipStream_t st);

@@ -64,8 +64,8 @@ struct mg_sim {
     int wK;
     long long wstep;
     StepCaps caps;     // the task's per-env slot caps
-    int step_variant;  // compiled LDS-resident step variant (0: HBM state)
-    int step_blk;      // envs per step workgroup
+    int step_form;     // step kernel form and envs per workgroup: a compiled pair of mg_stepforms.h
+    int step_blk;
     uint8_t *reset_mask; // device u8[N]: envs to auto-reset after the step
     // optional per-kernel timing (hipEvents on the launch stream)
     int timing;
@@ -262,67 +262,6 @@ static void layout(MGState &S, Carver &c, bool frames = true) {
 
 static hipStream_t as_stream(void *s) { return (hipStream_t)s; }
 
-// Per-env slot caps of a (task, variant): bodies, shapes, constraints, arbiter slots.
-static StepCaps step_caps(int task, int flags, int n_envs, const mg_library &lib) {
-    int nblk = 0, star_ok = 1;
-    switch (task) {
-    case MG_TASK_MOVE_TO_REGION: nblk = 0; break;
-    case MG_TASK_MOVE_TO_CORNER: nblk = 1; star_ok = (flags & MG_RAND_SHAPE_TYPE) != 0; break;
-    case MG_TASK_CLUSTER_COLOUR:
-    case MG_TASK_CLUSTER_SHAPE: nblk = (flags & MG_RAND_SHAPE_COUNT) ? 10 : 8; break;
-    case MG_TASK_MAKE_LINE: nblk = 4; break;
-    case MG_TASK_FIND_DUPE: nblk = 7; break;
-    case MG_TASK_FIX_COLOUR: nblk = 3; break;
-    case MG_TASK_PICK_AND_PLACE: nblk = 3; break;
-    default: nblk = (flags & MG_RAND_SHAPE_COUNT) ? 8 : 5; break;
-    }
-    const int per_blk = star_ok ? lib.block_nshapes[MG_SHAPE_STAR] : 1;
-    StepCaps c;
-    c.nb = 6 + nblk;
-    c.ns = 5 + nblk * per_blk;
-    c.nc = 10 + 2 * nblk;
-    int pairs = 4 * c.ns + 5 * (c.ns - 5) + ((c.ns - 5) * (c.ns - 6)) / 2; // walls, robot-block, block-block
-    c.na = pairs < MG_MAX_ARB ? (pairs + 3) / 4 * 4 : MG_MAX_ARB;
-    c.blk = 16;
-    (void)n_envs;
-    return c;
-}
-
-// Step kernel per scene (measured on MI355X, 8192 envs, ms per env-step of physics):
-// * compiled constraint lists (robot only / robot + one block): forms 5/6, 16 envs per 64-lane workgroup,
-//   4 lanes per env (4096 envs: MoveToRegion 0.62 ms, MoveToCorner 1.15; one env per lane, variants 1/2:
-//   0.73 / 1.42);
-// * every other scene (up to 8 blocks, runtime constraint lists): the cooperative LDS variant 4, one env
-//   per 64-lane wavefront with the order-free parts across lanes -- MatchRegions-TestAll 6.0 ms (variant
-//   3, one env per single-lane workgroup: 10.6; HBM-state kernel, 64 envs per wavefront: 21.1),
-//   ClusterColour-Demo 8.6 ms (variant 3: 15.1; HBM-state kernel: 10.7).
-static int pick_step_variant(const StepCaps &c, int n_envs, int task) {
-    (void)task;
-    int v = mg_step_variant(c, n_envs);
-    if (v == 3) v = 4;
-    if (v == 1 || v == 2) v += 4;
-    const char *ov = getenv("MG_STEP_VARIANT");
-    if (ov) { // experiments: 0 (HBM state), the scene's compiled variant (5 / 6; 1 / 2 in comparison builds),
-              // 3 / 4 (LDS runtime lists)
-        const int w = atoi(ov), base = mg_step_variant(c, n_envs);
-        if (w == 0 || ((w == base || w == 3) && mg_step_blk_ok(w, w == 3 ? 1 : 16)) || w == 4) v = w;
-        if ((base == 1 || base == 2) && w == base + 4) v = w;  // 5 / 6: the compiled lists, 4 lanes per env
-    }
-    return v;
-}
-
-// Robot-only scenes (variant 5) below 16 envs x CUs run 8 envs per workgroup: the grid then still reaches
-// every CU, and a workgroup takes half a CU's LDS, so render workgroups of another env chunk fit beside it
-// (the pipelined pool's 2048-env chunks: MoveToRegion 2.82 -> 2.84 M env-steps/s, profiles/r04_check7/).  At 4096 envs and more,
-// 16 (8 measured slower there: two workgroups per CU, 0.83 vs 0.61 ms).
-static int pick_step_blk(int variant, int n_envs, int cus) {
-    int b = variant == 0 ? 64 : variant == 3 || variant == 4 ? 1 : 16;
-    if ((variant == 5 || variant == 6) && n_envs < 16 * cus) b = 8;
-    const char *ov = getenv(variant == 0 ? "MG_STEP_BLK0" : "MG_STEP_BLK"); // experiments
-    if (ov && mg_step_blk_ok(variant, atoi(ov))) b = atoi(ov);
-    return b;
-}
-
 static int grid64(const mg_sim *s) { return (s->S.n_envs + 63) / 64; }
 
 static int render_lores(mg_sim *s, hipStream_t st, const uint8_t *mask) {
@@ -413,7 +352,6 @@ int mg_create(const mg_config *cfg, mg_sim **out) {
     s->S.cons_cap = MG_MAX_CONS;
     s->S.arb_cap = MG_MAX_ARB;
     s->S.max_tries = 10000; // geom.py:198
-    s->S.shw = nullptr;     // HBM-state kernels keep their narrowphase shapes in registers / scratch
     if (const char *mt = getenv("MG_DEBUG_MAX_TRIES")) s->S.max_tries = atoi(mt) > 0 ? atoi(mt) : 10000; // tests only
     s->reset_waves = getenv("MG_RESET_WAVES") ? atoi(getenv("MG_RESET_WAVES")) : 0;
     s->no_fused_reset = getenv("MG_FUSED_RESET") && atoi(getenv("MG_FUSED_RESET")) == 0;
@@ -441,11 +379,14 @@ int mg_create(const mg_config *cfg, mg_sim **out) {
     err = hipMalloc((void **)&s->dlib, sizeof(mg_library));
     if (err != hipSuccess) { (void)hipFree(s->pool); delete s; return set_err(-12, "mg_create: hipMalloc library"); }
     HIPC(hipMemcpy(s->dlib, cfg->library, sizeof(mg_library), hipMemcpyHostToDevice));
-    s->caps = step_caps(cfg->task, cfg->rand_flags, cfg->num_envs, *(const mg_library *)cfg->library);
-    s->step_variant = pick_step_variant(s->caps, cfg->num_envs, cfg->task);
+    // the step kernel's form and envs per workgroup (mg_stepforms.h); MG_STEP_VARIANT, MG_STEP_BLK (LDS forms) and
+    // MG_STEP_BLK0 (form 0) override them for experiments and tests
+    auto env_int = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
+    s->caps = step_caps(cfg->task, cfg->rand_flags, ((const mg_library *)cfg->library)->block_nshapes[MG_SHAPE_STAR]);
+    s->step_form = step_pick_form(s->caps, env_int("MG_STEP_VARIANT", -1));
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-    s->step_blk = pick_step_blk(s->step_variant, cfg->num_envs, cus);
+    s->step_blk = step_pick_blk(s->step_form, cfg->num_envs, cus, env_int("MG_STEP_BLK", 0), env_int("MG_STEP_BLK0", 0));
     err = hipMalloc((void **)&s->reset_mask, (size_t)s->S.N);
     if (err != hipSuccess) { (void)hipFree(s->pool); (void)hipFree(s->dlib); delete s; return set_err(-12, "mg_create: hipMalloc mask"); }
     HIPC(hipMemset(s->reset_mask, 0, (size_t)s->S.N));
@@ -544,12 +485,12 @@ int mg_step(mg_sim *s, const uint8_t *actions, void *stream) {
     // robot scenes without layout randomisation: the step kernel runs the auto-reset itself (mg_stepk.h)
     const bool layout = (s->flags & (MG_RAND_LAYOUT_MINOR | MG_RAND_LAYOUT_FULL)) != 0;
     cfg.fused_reset = s->auto_reset && !s->shadow_ok && !layout && !s->no_fused_reset &&
-                      ((s->task == MG_TASK_MOVE_TO_REGION && s->step_variant == 5) ||
-                       (s->task == MG_TASK_MOVE_TO_CORNER && s->step_variant == 6));
+                      ((s->task == MG_TASK_MOVE_TO_REGION && s->step_form == 5) ||
+                       (s->task == MG_TASK_MOVE_TO_CORNER && s->step_form == 6));
     hipEvent_t *ev = nullptr;
     if (s->timing && s->ev_used + 4 <= s->ev.size()) { ev = &s->ev[s->ev_used]; s->ev_used += 4; }
     if (ev) HIPC(hipEventRecord(ev[0], st));
-    HIPC(mg_launch_step(s->S, s->dlib, cfg, s->step_variant, s->step_blk, s->max_steps, s->auto_reset, actions, s->out.reward,
+    HIPC(mg_launch_step(s->S, s->dlib, cfg, s->step_form, s->step_blk, s->max_steps, s->auto_reset, actions, s->out.reward,
                         s->out.done, s->out.eval_score, s->reset_mask, st));
     if (ev) HIPC(hipEventRecord(ev[1], st));
     if (s->auto_reset) {
@@ -756,15 +697,9 @@ int mg_num_envs(const mg_sim *s) { return s ? s->S.n_envs : -22; }
 
 int mg_step_form(const mg_sim *s, int32_t *out) {
     if (!s || !out) return set_err(-22, "mg_step_form: null argument");
-    out[0] = s->step_variant; out[1] = s->step_blk;
-    out[2] = s->caps.nb; out[3] = s->caps.ns; out[4] = s->caps.nc; out[5] = s->caps.na;
-    if (s->step_variant == 5 || s->step_variant == 6) {   // the quad forms' compile-time caps (mg_stepk.h)
-        const int q[2][4] = {{6, 5, 10, 20}, {7, 6, 12, 32}};
-        for (int k = 0; k < 4; k++) out[2 + k] = q[s->step_variant - 5][k];
-    } else if (s->step_variant != 0) {
-        const StepCaps c = step_variant_caps(s->step_variant);
-        out[2] = c.nb; out[3] = c.ns; out[4] = c.nc; out[5] = c.na;
-    }
+    const StepCaps c = step_reported_caps(s->step_form, s->caps);
+    out[0] = s->step_form; out[1] = s->step_blk;
+    out[2] = c.nb; out[3] = c.ns; out[4] = c.nc; out[5] = c.na;
     return 0;
 }
 

@@ -9,8 +9,6 @@
 #pragma once
 #include "mg_common.h"
 
-struct ShapeW;  // mg_phys.h
-
 struct MGState {
     int N;      // padded env count (multiple of 64); row stride of every [slot][N] array
     int n_envs; // live env count
@@ -74,9 +72,6 @@ struct MGState {
     // body's geometry reaches copies it instead of being resolved (render_kernel)
     uint8_t *scache;         // [N][96*96*3]
     uint8_t *scache_ok;      // [N] 1: scache holds this episode's static layer
-    // LDS views of the compile-time robot scenes: 3 world-space shapes per lane (narrowphase operands:
-    // the queried shape, a wall, the other shape) in LDS instead of per-lane scratch; null elsewhere
-    ShapeW *shw;
 };
 
 // constraint parameter slots (cp[k][c][env])

@@ -1,7 +1,7 @@
 // mg_stepk.h -- the step kernel template (action decode, 10 x [Robot.update + cpSpaceStep], episode
 // counter, score) and its launcher.  Each form is instantiated in its own translation unit
 // (mg_step_quad.hip: 5 / 6, mg_step_v4.hip: 4, mg_step_hbm.hip: 0) so they compile in parallel;
-// mg_physics.hip dispatches.
+// mg_physics.hip dispatches.  The forms, their slot caps and the LDS view's arrays: mg_stepforms.h.
 #pragma once
 #include <cstdio>
 #include "mg_launch.h"
@@ -10,67 +10,13 @@
 #include "mg_score.h"
 #include "mg_reset.h"
 
-// slot caps of every compiled form: the LDS variants of mg_launch.h, plus the QL-lanes-per-env forms of the
-// compile-time scenes (5: the caps of 1 with two world-shape slots per lane in LDS -- 2 x 64 per workgroup,
-// so 128 / blk per env; 6: the caps of 2, world shapes in per-lane locals as there)
-// Form 5's narrowphase operands (two ShapeW per lane) in LDS (1, rounds 2-5) or per-lane locals (0, round 6, as
-// form 6).  The LDS slots were 51 of the 8-env workgroup's 78 KB; without them the step workgroup takes 27 KB, so
-// more of the other chunk's render workgroups co-run beside it: step kernel 0.400 -> 0.415 ms alone, 0.61 -> 0.52 ms
-// co-running, MoveToRegion 3.04 -> 3.16 M env-steps/s (profiles/r06_q5)
-#ifndef MG_Q5_LDS_SHAPES
-#define MG_Q5_LDS_SHAPES 0
-#endif
-__host__ __device__ constexpr StepCaps step_form_caps(int v, int blk) {
-    return v == 5 ? StepCaps{6, 5, 10, 20, 16, MG_Q5_LDS_SHAPES ? 128 / blk : 0}
-         : v == 6 ? StepCaps{7, 6, 12, 32, 16, 0} : step_variant_caps(v);
-}
-
 // ---- LDS-resident substeps ------------------------------------------------
-// The 10 substeps of an env-step touch only the env's bodies, shapes,
-// constraints, arbiters and a few scalars.  They are copied once per env-step
-// from HBM ([slot][N] arrays) into LDS ([slot][BLK] arrays, one column per lane)
-// and the MGState "view" V points there with V.N = BLK and e = lane, so the same
-// device code runs against LDS; everything is copied back before scoring and
-// the in-place reset (which use the HBM state).  A lane only touches its own
-// column, so no barrier is needed.
-template <typename T>
-__device__ __forceinline__ T *carve(unsigned char *base, size_t &off, size_t count) {
-    off = (off + 15) & ~(size_t)15;
-    T *p = (T *)(base + off);
-    off += count * sizeof(T);
-    return p;
-}
-
-__device__ __forceinline__ void carve_view(MGState &V, unsigned char *smem, const StepCaps &c, int blk) {
-    size_t off = 0;
-    const size_t B = (size_t)c.nb * blk, SH = (size_t)c.ns * blk, C = (size_t)c.nc * blk, A = (size_t)c.na * blk;
-    V.bpx = carve<double>(smem, off, B); V.bpy = carve<double>(smem, off, B); V.bvx = carve<double>(smem, off, B);
-    V.bvy = carve<double>(smem, off, B); V.ba = carve<double>(smem, off, B); V.bw = carve<double>(smem, off, B);
-    V.bvbx = carve<double>(smem, off, B); V.bvby = carve<double>(smem, off, B); V.bwb = carve<double>(smem, off, B);
-    V.brc = carve<double>(smem, off, B); V.brs = carve<double>(smem, off, B); V.bminv = carve<double>(smem, off, B);
-    V.biinv = carve<double>(smem, off, B); V.bacache = carve<double>(smem, off, B);
-    V.sr = carve<double>(smem, off, SH); V.su = carve<double>(smem, off, SH); V.sbbl = carve<double>(smem, off, SH);
-    V.sbbb = carve<double>(smem, off, SH); V.sbbr = carve<double>(smem, off, SH); V.sbbt = carve<double>(smem, off, SH);
-    V.cp = carve<double>(smem, off, (size_t)CP_NUM * C);
-    V.anx = carve<double>(smem, off, A); V.any = carve<double>(smem, off, A); V.au = carve<double>(smem, off, A);
-    V.acon = carve<double>(smem, off, (size_t)2 * AC_NUM * A); V.ahash = carve<uint64_t>(smem, off, 2 * A);
-    V.curr_dt = carve<double>(smem, off, blk); V.target_speed = carve<double>(smem, off, blk);
-    V.rel_turn = carve<double>(smem, off, blk); V.target_finger = carve<double>(smem, off, blk);
-    V.akey = carve<int32_t>(smem, off, A); V.astamp = carve<uint32_t>(smem, off, A);
-    V.nbodies = carve<int32_t>(smem, off, blk); V.nshapes = carve<int32_t>(smem, off, blk);
-    V.ncons = carve<int32_t>(smem, off, blk); V.nactive = carve<int32_t>(smem, off, blk);
-    V.stamp = carve<uint32_t>(smem, off, blk); V.overflow = carve<int32_t>(smem, off, blk);
-    V.robot_body0 = carve<int32_t>(smem, off, blk); V.robot_cons0 = carve<int32_t>(smem, off, blk);
-    V.sgroup = carve<int16_t>(smem, off, SH); V.shash = carve<int16_t>(smem, off, SH);
-    V.sbody = carve<int8_t>(smem, off, SH); V.spoly = carve<int8_t>(smem, off, SH);
-    V.ctype = carve<int8_t>(smem, off, C); V.ca = carve<int8_t>(smem, off, C); V.cb = carve<int8_t>(smem, off, C);
-    V.astate = carve<int8_t>(smem, off, A); V.acount = carve<int8_t>(smem, off, A); V.asa = carve<int8_t>(smem, off, A);
-    V.asb = carve<int8_t>(smem, off, A); V.active = carve<int8_t>(smem, off, A);
-    V.shw = c.shw ? carve<ShapeW>(smem, off, (size_t)c.shw * blk) : nullptr;
-    V.N = blk;
-    V.cons_cap = c.nc;
-    V.arb_cap = c.na;
-}
+// The substeps run on the LDS view (carve_view, mg_stepforms.h) with V.N = BLK and e = lane; everything is
+// copied back before scoring and the in-place reset (which use the HBM state).  The narrowphase operands (two
+// ShapeW per lane) stay in per-lane locals: form 5 kept them in LDS in rounds 2-5, 51 of the 8-env workgroup's
+// 78 KB; without them the step workgroup takes 27 KB, so more of the other chunk's render workgroups co-run
+// beside it: step kernel 0.400 -> 0.415 ms alone, 0.61 -> 0.52 ms co-running, MoveToRegion 3.04 -> 3.16 M
+// env-steps/s (profiles/r06_q5).
 
 // rows [0, rows) of a [row][N] HBM array <-> [row][BLK] LDS array (lane's column); for the
 // cp / acon / ahash blocks the HBM row of LDS row (k, r) is k * hcap + r
@@ -164,9 +110,7 @@ MG_DEV void xq(T *lds, T *hbm, int blk, int lane, int N, int e, int sub, bool in
     }
 }
 
-// (QL = 64, lane = 0, sub = the thread: the cooperative form, one env per wavefront; CONS: its runtime constraint
-// list is transferred too)
-template <int NB, int NS, int NC, int NA, int QL, bool CONS = false>
+template <int NB, int NS, int NC, int NA, int QL>
 __device__ __forceinline__ void xfer_state_quad(const MGState &S, const MGState &V, int lane, int e, int sub, bool in) {
     const int blk = V.N, N = S.N;
     // groups of a few arrays are scheduled on their own (sched_barrier): their loads are in flight together,
@@ -232,7 +176,6 @@ __device__ __forceinline__ void xfer_state_quad(const MGState &S, const MGState 
     if (in) {   // read-only during the substeps
         XQ(bminv, NB); XQ(biinv, NB); XQ(sr, NS); XQ(su, NS); XQ_GROUP();
         XQ(sgroup, NS); XQ(shash, NS); XQ(sbody, NS); XQ(spoly, NS);
-        if constexpr (CONS) { XQ(ctype, NC); XQ(ca, NC); XQ(cb, NC); }
         XQ_GROUP();
     }
 #undef XQ_GROUP
@@ -280,8 +223,8 @@ __global__ void __launch_bounds__(64) step_kernel(MGState S, const mg_library *_
                                                   int auto_reset, const uint8_t *__restrict__ actions, float *reward,
                                                   uint8_t *done, double *eval_score, uint8_t *reset_mask) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr StepCaps C = step_form_caps(VAR, BLK);
-    static_assert(VAR == 0 || VAR == 4 || VAR == 5 || VAR == 6, "compiled forms: 0 (HBM state), 4 (cooperative), 5 / 6");
+    constexpr StepCaps C = step_form_caps(VAR);
+    static_assert(mg_step_blk_ok(VAR, BLK), "not a pair of MG_STEP_FORMS (mg_stepforms.h)");
     constexpr bool LDS = VAR != 0;
     constexpr bool COOP = VAR == 4;            // one env per workgroup of 64 lanes
     constexpr bool QUAD = VAR == 5 || VAR == 6; // QL lanes per env, BLK envs in one 64-lane workgroup
@@ -334,7 +277,7 @@ __global__ void __launch_bounds__(64) step_kernel(MGState S, const mg_library *_
             if (!fits && sub == 0) { // an empty scene in the env's column: nothing indexes past the caps
                 V.nbodies[lane] = 0; V.nshapes[lane] = 0; V.ncons[lane] = 0; V.nactive[lane] = 0;
             }
-            env_substeps_quad<NCS, QL, (C.shw > 0)>(V, L, lane, sub, a, P);
+            env_substeps_quad<NCS, QL>(V, L, lane, sub, a, P);
             if (own) xfer_state(S, V, C, lane, e, false, false, sub, QL);   // stores: no latency chain to batch
             // the env's lane 0 scores from HBM rows its sibling lanes just wrote back: order them
             // by the memory model, not by one wavefront's in-order memory pipe
@@ -378,8 +321,7 @@ template <int VAR, int BLK>
 hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, int max_steps, int auto_reset,
                                   const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
                                   uint8_t *reset_mask, hipStream_t st) {
-    constexpr StepCaps C = step_form_caps(VAR, BLK);
-    const size_t lds = VAR == 0 ? 0 : mg_step_lds_bytes(C, BLK);
+    constexpr size_t lds = VAR == 0 ? 0 : mg_step_lds_bytes(step_form_caps(VAR), BLK);
     static bool attr_set = false;
     if (VAR != 0 && !attr_set) {
         hipError_t err = hipFuncSetAttribute((const void *)step_kernel<VAR, BLK>,
@@ -390,7 +332,7 @@ hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, i
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL((step_kernel<VAR, BLK>), dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 4 || VAR == 5 || VAR == 6 ? 64 : BLK), lds, st, S, L, cfg,
+    hipLaunchKernelGGL((step_kernel<VAR, BLK>), dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 0 ? BLK : 64), lds, st, S, L, cfg,
                        max_steps, auto_reset, actions, reward, done, eval_score, reset_mask);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
@@ -398,3 +340,8 @@ hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, i
                 (S.n_envs + BLK - 1) / BLK, lds, hipGetErrorString(err));
     return err;
 }
+
+// a translation unit instantiates its row of the form table: MG_STEP_FORMS_QUAD(MG_STEP_INSTANTIATE)
+#define MG_STEP_INSTANTIATE(F, B) \
+    template hipError_t launch_step_var<F, B>(const MGState &, const mg_library *, TaskCfg, int, int, const uint8_t *, \
+                                              float *, uint8_t *, double *, uint8_t *, hipStream_t);

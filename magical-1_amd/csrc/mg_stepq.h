@@ -1,7 +1,7 @@
 // mg_stepq.h -- cpSpaceStep with QL lanes per env (the compile-time robot scenes, step forms 5 and 6).
 //
-// The forms 1 / 2 run one env per lane, 16 envs in a 16-lane wave per CU: every phase of an env's
-// substep is one lane's serial chain.  Here each env owns QL = 64 / BLK lanes of the workgroup's one
+// With one env per lane (the forms deleted in round 5: 16 envs in a 16-lane wave per CU) every phase of an
+// env's substep is one lane's serial chain.  Here each env owns QL = 64 / BLK lanes of the workgroup's one
 // wavefront (16 envs x 4 lanes) and the order-free phases are split over them:
 //   * position integration and rotation caches (quad_body: the robot body, fingers and block -- the bodies
 //     that need the correctly rounded sincos -- one per lane, side by side), cached shape BBs (shape k on
@@ -89,11 +89,9 @@ MG_DEV bool quad_candidate(const MGState &S, const mg_library *L, int e, int i, 
 // at a time in mask order (the q-th lowest on lane q): collide(), then lane 0 applies the arbiter updates in
 // canonical order from its siblings' results (cross-lane reads).  The same collide() calls and the same
 // arbiter updates in the same order as a serial sweep of the candidates, so bit-identical.
-template <int NCS, int QL, bool LDS_SHAPES>
+template <int NCS, int QL>
 MG_DEV void narrowphase_quad(const MGState &S, const mg_library *L, int e, int sub, int ns) {
-    ShapeW locA, locB;
-    ShapeW &A = LDS_SHAPES ? S.shw[2 * QL * e + 2 * sub] : locA;
-    ShapeW &B = LDS_SHAPES ? S.shw[2 * QL * e + 2 * sub + 1] : locB;
+    ShapeW A, B;
     const int ntot = 4 * ns + (ns * (ns - 1)) / 2;
     for (int w0 = 0; w0 < ntot; w0 += 64) {
         const int wn = ntot - w0 < 64 ? ntot - w0 : 64;
@@ -168,7 +166,7 @@ MG_DEV void narrowphase_quad(const MGState &S, const mg_library *L, int e, int s
     }
 }
 
-template <int NCS, int QL, bool LDS_SHAPES>
+template <int NCS, int QL>
 MG_DEV void space_step_quad(const MGState &S, const mg_library *L, int e, int sub, double dt, MGProf &P) {
     __syncthreads();   // the previous substep's solver / robot update are done
     const double prev_dt = S.curr_dt[e];
@@ -187,7 +185,7 @@ MG_DEV void space_step_quad(const MGState &S, const mg_library *L, int e, int su
     for (int k = sub; k < ns; k += QL) shape_update_bb(S, L, e, k);
     __syncthreads();
     MG_PP(P, 1);
-    narrowphase_quad<NCS, QL, LDS_SHAPES>(S, L, e, sub, ns);
+    narrowphase_quad<NCS, QL>(S, L, e, sub, ns);
     __syncthreads();
     MG_PP(P, 2);
     for (int i = sub; i < S.arb_cap; i += QL) {   // cached arbiter filter
@@ -210,7 +208,7 @@ MG_DEV void space_step_quad(const MGState &S, const mg_library *L, int e, int su
 }
 
 // Robot.set_action + 10 x (Robot.update, cpSpaceStep) with QL lanes per env
-template <int NCS, int QL, bool LDS_SHAPES>
+template <int NCS, int QL>
 __device__ __forceinline__ void env_substeps_quad(const MGState &V, const mg_library *L, int ev, int sub, int a,
                                                   MGProf &P) {
     // robot.update() before every space.step() (base_env.py:248-255).  From the second substep on it runs on
@@ -228,7 +226,7 @@ __device__ __forceinline__ void env_substeps_quad(const MGState &V, const mg_lib
     const double dt = L->dt;
     for (int i = 0; i < 10; i++) {
         MG_PP(P, 0);
-        space_step_quad<NCS, QL, LDS_SHAPES>(V, L, ev, sub, dt, P);   // starts with a workgroup barrier
+        space_step_quad<NCS, QL>(V, L, ev, sub, dt, P);   // starts with a workgroup barrier
         if (sub == 0 && i < 9) robot_update<true>(V, L, ev);
     }
     __syncthreads();

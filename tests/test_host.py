@@ -517,6 +517,55 @@ def test_bench_byte_models():
         del os.environ["MG_STEP_VARIANT"]
 
 
+def test_step_forms_header(tmp_path):
+    """csrc/mg_stepforms.h on its own under the host compiler with ASan + UBSan (tests/step_forms_probe.cpp, a child
+    process).  The LDS view that carve_view carves for every LDS (form, envs per workgroup) pair of the table: arrays
+    in table order, 16-byte aligned, each starting at or after its predecessor's end (so pairwise disjoint), ending
+    -- rounded up to 16 -- at mg_step_lds_bytes, the dynamic LDS the launch asks for, within the 160 KB of a
+    workgroup and at the sizes of the function this table replaced.  And the selection (scene form, MG_STEP_VARIANT /
+    MG_STEP_BLK / MG_STEP_BLK0 overrides, envs per workgroup by grid size, caps mg_step_form reports) over tasks x
+    flags x overrides x env counts against tests/golden/step_forms_select.json, recorded from the functions this
+    header replaced."""
+    import json
+    from magical_amd import tables
+    exe = str(tmp_path / "step_forms_probe")
+    cc = subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "magical-1_amd", "csrc"),
+                         os.path.join(ROOT, "tests", "step_forms_probe.cpp"), "-o", exe],
+                        capture_output=True, text=True, timeout=300)
+    assert cc.returncode == 0, cc.stderr[-2000:]
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "step_forms_select.json")))
+    star = int(tables.build_library().block_nshapes[6])   # MG_SHAPE_STAR
+    assert star == golden["star_shapes"]
+    run = subprocess.run([exe, str(star)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and not run.stderr, run.stderr[-2000:]
+    got = json.loads(run.stdout)
+    pairs = [tuple(p) for p in got["pairs"]]
+    assert sorted(pairs) == [(0, 1), (0, 8), (0, 64), (4, 1), (5, 8), (5, 16), (6, 8), (6, 16)] and len(set(pairs)) == 8
+    lds_bytes = {(4, 1): 19184, (5, 16): 110336, (5, 8): 55184, (6, 16): 159104, (6, 8): 79552}
+    form_caps = {4: (14, 53, 26, 48), 5: (6, 5, 10, 20), 6: (7, 6, 12, 32)}   # test_bench_record_fields' keys
+    views = {(v["form"], v["blk"]): v for v in got["views"]}
+    assert set(views) == {p for p in pairs if p[0] != 0} == set(lds_bytes)
+    names = [a[0] for a in got["views"][0]["arrays"]]
+    assert len(set(names)) == len(names) == 52
+    for (form, blk), v in views.items():
+        nb, ns, nc, na = form_caps[form]
+        assert (v["N"], v["cons_cap"], v["arb_cap"]) == (blk, nc, na)
+        counts = {m * r * blk for m in (1, 2, 20) for r in (nb, ns, nc, na, 1)}   # 20: CP_NUM, 2 * AC_NUM
+        assert [a[0] for a in v["arrays"]] == names
+        end = 0
+        for name, off, esize, count in v["arrays"]:
+            assert off % 16 == 0 and off >= end and esize in (1, 2, 4, 8) and count in counts, (form, blk, name)
+            end = off + esize * count
+        assert (end + 15) // 16 * 16 == v["lds_bytes"] == lds_bytes[form, blk] <= 163840, (form, blk)
+    rows = golden["rows"]
+    assert len(rows) == 9 * 4 * 25 and len(got["select"]) == len(rows)
+    for g, w in zip(got["select"], rows):
+        assert g == w, dict(zip(golden["columns"], zip(g[:10] + [g[10:]], w[:10] + [w[10:]])))
+    for r in rows:   # the caps reported with an LDS form are the form's
+        assert r[5] == 0 or tuple(r[6:10]) == form_caps[r[5]]
+
+
 def test_bench_plain_run_measures_no_cpu_baseline():
     """Without --full the CPU baseline is not measured (--dry-run: the launcher path of one rank, no GPU)."""
     import json

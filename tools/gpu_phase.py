@@ -59,8 +59,7 @@ if v[63]:
 tot = sum(v[32:42])
 # one timer per workgroup (its first lane): the robot scenes' quad forms run blk envs per workgroup (16, or 8 below
 # 16 envs per CU), the cooperative form one env per workgroup
-robot = name.startswith(("MoveToRegion", "MoveToCorner"))
-blk = int(os.environ.get("MG_STEP_BLK", 0)) or ((16 if n >= 16 * 256 else 8) if robot else 1)
+blk = vec.step_form()[1]
 wgs = (n + blk - 1) // blk
 print(f"physics: total {tot / 1e6:.1f}M ticks, {wgs} workgroups of {blk} envs")
 for i, nm in enumerate(P):
