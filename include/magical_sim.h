@@ -167,6 +167,36 @@ int mg_restack_window(const uint8_t *recv, int32_t world, int32_t n, int64_t ran
 int mg_bind_window(mg_sim *sim, uint8_t *ring_allo, uint8_t *ring_ego, int32_t K);
 /* *slot = the window's first slot for the current outputs ((w + K - 3) % K), -1 when no ring is bound */
 int mg_window_start(const mg_sim *sim, int32_t *slot);
+/* Env state snapshots.  A blob holds `count` env records behind a 256-byte header; a record is everything that makes
+ * an env's continuation bit-identical: every per-env state row (bodies, shapes, constraints, arbiter tables with
+ * their warm-start accumulators, stamp, curr_dt, entities, episode_steps, PickAndPlace's target, the MT19937 key and
+ * position), the error flags, the render's per-episode scratch (class chain level, static layer and its valid flag)
+ * and the LoRes frame history with its ring heads.  The blob is opaque and relocatable (copy it, save it, load it
+ * on another process); its layout is magical-1_amd/csrc/mg_snapshot.h.  Header, little-endian: u32 magic "MGSN",
+ * u32 layout version, i32 task, rand_flags, preproc, the MG_MAX_* caps (bodies, shapes, constraints, arbiters,
+ * entities), i32 rows, i32 frames per record, i64 state bytes per record, i64 record bytes, i64 record count, i64
+ * blob bytes, zero padding.
+ * Supported: materialised stacks and the unwrapped surface.  A sim with window rings (mg_bind_window) or
+ * frames_only outputs returns -22 from both calls: its frame stacks live with the caller / the receivers.
+ *
+ * mg_snapshot_bytes: bytes of a blob of n records for cfg's task and preprocessor = 256 + n * record bytes (the
+ * record size depends on the preprocessor only, through the frames it carries); host-only, touches no GPU. */
+int64_t mg_snapshot_bytes(const mg_config *cfg, int32_t n);
+/* gather: record k of the blob <- env envs[k] (host i32[n], each in [0, num_envs), 1 <= n <= num_envs; NULL = all
+ * envs in order, n = num_envs).  blob_dev: device, 16-byte aligned, mg_snapshot_bytes(cfg, n) bytes.  The current
+ * frame of a view that keeps no ring (LoRes4E / LoRes3EA allo, LoRes4A ego) is read from the bound output, which
+ * must still hold the latest observation.  Enqueued on the stream; the index array is consumed before returning. */
+int mg_snapshot(mg_sim *sim, const int32_t *envs, int32_t n, uint8_t *blob_dev, void *stream);
+/* scatter: env envs[k] <- record recs[k] of the blob, k < n (host arrays; recs NULL = k, and may repeat: one record
+ * broadcast to many envs; envs NULL = 0..n-1, else distinct and in range).  The header is validated first, through one
+ * small device-to-host copy that synchronises the stream, before any kernel is launched: a blob of another task,
+ * rand_flags, preprocessor, slot caps or layout version, a bad magic value or a bad index returns -22 and leaves the
+ * sim untouched.  The blob's contents behind a valid header are trusted.  Then the bound observation outputs of the
+ * restored envs (obs_allo, obs_ego, obs_past, PickAndPlace's target) hold the observation the env had when
+ * recorded, rebuilt from the restored frame history (nothing is rendered: a render would push a frame); reward, done
+ * and eval_score describe a step, not a state, and stay as they are.  The many-block tasks' next-layout shadow of
+ * the restored envs is prepared again from the restored RNG state, as after a masked mg_reset. */
+int mg_restore(mg_sim *sim, const uint8_t *blob_dev, const int32_t *envs, const int32_t *recs, int32_t n, void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

@@ -20,7 +20,8 @@ _COMMON = ["mg_common.h", "mg_math.h", "mg_state.h", "mg_stepforms.h", "mg_launc
 _PHYS = _COMMON + ["mg_phys.h", "mg_step.h"]
 _STEP = _PHYS + ["mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h"]
 UNITS = {  # translation unit -> headers it depends on (one unit per kernel family: they compile in parallel)
-    "mg_sim.hip": _COMMON + ["mg_phys.h"],
+    "mg_sim.hip": _COMMON + ["mg_phys.h", "mg_snapshot.h"],
+    "mg_snapshot.hip": ["mg_common.h", "mg_snapshot.h"],
     "mg_physics.hip": _COMMON,
     "mg_reset.hip": _COMMON + ["mg_phys.h", "mg_reset.h"],
     "mg_step_v4.hip": _STEP,

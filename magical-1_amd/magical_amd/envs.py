@@ -123,6 +123,7 @@ class VecMagicalEnv:
         handle = ctypes.c_void_p()
         native.check(self.lib.mg_create(ctypes.byref(cfg), ctypes.byref(handle)))
         self.handle = handle
+        self._cfg = cfg   # (mg_snapshot_bytes sizes a blob from it)
         n, dev = self.num_envs, self.device
         u8 = dict(dtype=torch.uint8, device=dev)
         wa, we = window_views(self.spec) if window and pp is not None else (False, False)
@@ -309,6 +310,64 @@ class VecMagicalEnv:
         native.check(self.lib.mg_get_errors(self.handle, ctypes.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    # -- snapshots ---------------------------------------------------------------
+    def snapshot_bytes(self, n=None):
+        """Bytes of a snapshot blob of n (default: all) envs of this env (mg_snapshot_bytes; no GPU work)."""
+        nbytes = self.lib.mg_snapshot_bytes(ctypes.byref(self._cfg), self.num_envs if n is None else int(n))
+        if nbytes < 0:
+            native.check(int(nbytes))
+        return int(nbytes)
+
+    def snapshot(self, envs=None, out=None):
+        """Record the state of the envs in `envs` (a sequence of indices; default: every env in order) into a
+        `magical_amd.snapshot.Snapshot` on this device: record k holds env envs[k] -- physics, RNG stream, episode
+        phase, frame stacks, everything that makes `restore` + the same actions bit-identical to not having
+        stopped.  Enqueued on the current stream.  The outputs must still hold the latest observation (they are
+        the env's own buffers unless bind_outputs replaced them).  Not with window=True or frames_only outputs
+        (NativeError).  Host-side state of wrappers is not part of it: magical_amd.sb3.MagicalVecEnv's Monitor
+        statistics and dist.ShardedVecEnv's rings / ranks are out of scope.  out: a uint8 device tensor of
+        snapshot_bytes(n) bytes to fill instead of a new one."""
+        from .snapshot import Snapshot
+        n = self.num_envs if envs is None else len(envs)
+        nbytes = self.snapshot_bytes(n)
+        blob = out if out is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if blob.numel() != nbytes or blob.dtype != torch.uint8 or blob.device != self.device or not blob.is_contiguous():
+            raise ValueError(f"snapshot: out must be a contiguous uint8 tensor of {nbytes} bytes on {self.device}")
+        arr = None if envs is None else (ctypes.c_int32 * n)(*[int(e) for e in envs])
+        native.check(self.lib.mg_snapshot(self.handle, arr, n, ctypes.c_void_p(blob.data_ptr()), self._stream()))
+        return Snapshot(blob, count=n)
+
+    def restore(self, snap, envs=None, recs=None):
+        """Put recorded envs back: env envs[k] <- record recs[k] of `snap` (recs default 0, 1, ..; it may repeat a
+        record to broadcast it; envs default 0 .. n-1, else distinct), and return the observation, in which the
+        restored envs show what they showed when recorded (reward / done / eval_score describe a step and keep
+        their values).  A `PoolSnapshot` of a PipelinedVecEnv with the same env order restores every env (envs and
+        recs must be None).  The blob's header is checked on the host and again by the library against this env's
+        task, variant flags and preprocessor: a mismatch, a truncated blob or a bad index raises NativeError and
+        leaves the env untouched.  Synchronises the current stream once (the header check)."""
+        from .snapshot import PoolSnapshot
+        if isinstance(snap, PoolSnapshot):
+            if envs is not None or recs is not None or len(snap) != self.num_envs:
+                raise ValueError("restore: a PoolSnapshot restores every env of a batch of the same size, in order")
+            for k, chunk in enumerate(snap.chunks):
+                self._restore(chunk, range(snap.bounds[k], snap.bounds[k + 1]), None)
+        else:
+            self._restore(snap, envs, recs)
+        if self.spec.preproc is None:
+            self.render_full(out=self.full)
+        return self._obs()
+
+    def _restore(self, snap, envs, recs):
+        if snap.device != self.device:
+            snap = snap.to(self.device)
+        snap.header   # host-side check: magic, version, truncation
+        if envs is not None and recs is not None and len(envs) != len(recs):
+            raise ValueError("restore: envs and recs must have the same length")
+        n = len(envs) if envs is not None else len(recs) if recs is not None else len(snap)
+        ea = None if envs is None else (ctypes.c_int32 * n)(*[int(e) for e in envs])
+        ra = None if recs is None else (ctypes.c_int32 * n)(*[int(r) for r in recs])
+        native.check(self.lib.mg_restore(self.handle, ctypes.c_void_p(snap.blob.data_ptr()), ea, ra, n, self._stream()))
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.mg_destroy(self.handle)
@@ -377,6 +436,21 @@ class MagicalEnv:
         d = bool(done[0].item())
         score = float(info["eval_score"][0].item())
         return self._np_obs(obs), float(rew[0].item()), d, {"eval_score": score}
+
+    def get_state(self):
+        """The env's whole state as bytes (a one-record snapshot blob, magical_amd.snapshot): physics, RNG, episode
+        phase and frame stacks.  Host-side wrapper statistics (e.g. an SB3 Monitor around this env) are not in it."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before get_state()")
+        return self._vec.snapshot().tobytes()
+
+    def set_state(self, state):
+        """Back to a state from get_state() (this env name; NativeError otherwise); returns its observation."""
+        from .snapshot import Snapshot
+        obs = self._vec.restore(Snapshot.frombytes(state))
+        if self._episode_steps is None:
+            self._episode_steps = 0
+        return self._np_obs(obs)
 
     def render(self, mode="rgb_array"):
         if mode != "rgb_array":

@@ -177,6 +177,43 @@ class PipelinedVecEnv:
         self.t += 1
         return self._obs(), self.buffers["reward"], self.buffers["done"], {"eval_score": self.buffers["eval_score"]}
 
+    def snapshot(self):
+        """The pool's state as a `magical_amd.snapshot.PoolSnapshot`: one blob per chunk, taken on the chunk's own
+        stream once every chunk's last step is done (wait()); the caller's stream is ordered after the blobs.  It
+        restores into a pool with the same chunking, or into a plain VecMagicalEnv of the same envs in the same
+        order (VecMagicalEnv.restore).  Materialised stacks only (not window=True)."""
+        from .snapshot import PoolSnapshot
+        self.wait()
+        blobs = [torch.empty(sim.snapshot_bytes(), dtype=torch.uint8, device=self.device) for sim in self.sims]
+        self._fork()
+        snaps = []
+        for sim, st, blob in zip(self.sims, self.streams, blobs):
+            with torch.cuda.stream(st):
+                snaps.append(sim.snapshot(out=blob))
+        self.wait()
+        return PoolSnapshot(snaps, self.bounds)
+
+    def restore(self, snap):
+        """Put every env of the pool back to a PoolSnapshot of the same chunking, each chunk on its own stream, and
+        return the observation (complete: the caller's stream is ordered after the chunks)."""
+        from .snapshot import PoolSnapshot
+        if not isinstance(snap, PoolSnapshot) or snap.bounds != self.bounds:
+            raise ValueError(f"PipelinedVecEnv.restore: a PoolSnapshot with chunk bounds {self.bounds}")
+        snap = snap.to(self.device)
+        self.wait()
+        self._fork()
+        b = self.bounds
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            with torch.cuda.stream(st):
+                sim.restore(snap.chunks[k])
+                if self.target_f is not None:
+                    self.target_f[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
+                    if self._target_out is not None:
+                        self._target_out[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
+        self.wait()
+        self._last = []
+        return self._obs()
+
     def _obs(self):
         from .envs import window_stack
         allo, ego, past = self.buffers.get("allo"), self.buffers.get("ego"), self.buffers.get("past_obs")
