@@ -197,6 +197,38 @@ int mg_snapshot(mg_sim *sim, const int32_t *envs, int32_t n, uint8_t *blob_dev, 
  * and eval_score describe a step, not a state, and stay as they are.  The many-block tasks' next-layout shadow of
  * the restored envs is prepared again from the restored RNG state, as after a masked mg_reset. */
 int mg_restore(mg_sim *sim, const uint8_t *blob_dev, const int32_t *envs, const int32_t *recs, int32_t n, void *stream);
+/* Lookahead: "what happens if these envs run these H actions", without touching the envs.  Caller-owned device
+ * outputs: */
+typedef struct {
+    double  *score;    /* f64[N]: the task's score_on_end_of_traj of the env's state after its last simulated step
+                          (whether or not that step ends the episode); required */
+    int32_t *steps;    /* i32[N]: env-steps simulated = min(H, max_episode_steps - episode_steps); NULL ok */
+    double  *bodies;   /* f64[N,16,6] as mg_get_bodies, of the final state; NULL ok */
+    int32_t *counts;   /* i32[N,4] as mg_get_bodies; NULL ok */
+    int32_t *errors;   /* i32[N]: error flags as mg_get_errors as they stand at the end of the rollout (the env's
+                          flags on entry plus any raised during it); the sim's own flags are not touched; NULL ok */
+} mg_lookahead_out;
+/* actions_dev: device u8[H][N] (step-major: step h of env e at h*N + e, N = num_envs), each in [0, 18);
+ * 0 <= H <= 4096.
+ * Every env is simulated from its current state for min(H, remaining) env-steps of physics only -- action decode
+ * plus 10 substeps each, exactly BaseEnv.step up to and including _phys_steps_on_frame (base_env.py:248-276) --
+ * with the operations of mg_step in the same order, so the final state has the bits that as many mg_step calls
+ * would give it.  No render, no frame push, no reward / done / eval_score outputs, no auto-reset and no fused
+ * reset.  An env whose episode would end inside the horizon stops at its terminal step, and its score is what
+ * mg_step would have reported as eval_score there; with max_episode_steps <= 0 nothing ends early.  An env with
+ * 0 remaining steps simulates nothing and is scored as it stands.  H = 0 is "score only": every env's current
+ * state is scored, steps = 0, and actions_dev may be NULL.
+ * The sim is observationally untouched: state rows, RNG, episode_steps, error flags, frame rings, window rings,
+ * bound outputs, the next-layout shadow and its pending work are unchanged, and a following mg_step gives the
+ * same bytes as if the call had not happened.  It works in every mode (window rings, frames_only outputs,
+ * auto_reset 0 or 1, the unwrapped surface) and touches no frames.
+ * The rollout runs on a scratch copy of the state that the sim owns: allocated by the first call (that call
+ * alone allocates and therefore synchronises the device), reused by later ones, freed in mg_destroy.  Everything
+ * else is enqueued on `stream` with no host sync.  Calls on one stream reuse the scratch in order; two lookaheads
+ * in flight on different streams of one handle are not supported (one handle, one host thread, as everywhere).
+ * Returns -22 and launches nothing for a null sim / out / out->score, a null actions_dev with H > 0, or H
+ * outside [0, 4096]. */
+int mg_lookahead(mg_sim *sim, const uint8_t *actions_dev, int32_t H, const mg_lookahead_out *out, void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

@@ -51,6 +51,15 @@ hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, i
 hipError_t mg_launch_step(const MGState &S, const mg_library *L, TaskCfg cfg, int form, int blk, int max_steps,
                           int auto_reset, const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
                           uint8_t *reset_mask, hipStream_t st);
+// mg_lookahead: H env-steps of physics on S, the sim's scratch copy of the state, then the outputs of LookOut (the
+// device pointers of mg_lookahead_out; score is never null).  actions: u8[H][n_envs].  One compiled pair per pair of
+// the step kernel (defined in mg_lookahead.h, instantiated in mg_look_*.hip, dispatched in mg_lookahead.hip)
+struct LookOut { double *score; int32_t *steps; double *bodies; int32_t *counts; int32_t *errors; };
+template <int VAR, int BLK>
+hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
+                                int H, const LookOut &out, hipStream_t st);
+hipError_t mg_launch_lookahead(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
+                               const uint8_t *actions, int H, const LookOut &out, hipStream_t st);
 hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderOut &ro, int mode, hipStream_t st);
 hipError_t mg_launch_compose3ea(const MGState &S, const uint8_t *obs_allo, const uint8_t *mask, uint8_t *obs_past,
                                 hipStream_t st);

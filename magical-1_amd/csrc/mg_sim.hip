@@ -77,6 +77,14 @@ struct mg_sim {
     char *snap_stage, *snap_dev;
     hipEvent_t ev_snap;
     int snap_inflight;
+    // lookahead (mg_lookahead): LK is a third copy of the per-env state (the shadow's layout: no frame rings), the
+    // scratch its rollouts run on; allocated by the first call.  look_rows: the state rows a rollout needs copied
+    // (every row but the MT19937 key -- physics and scoring draw no numbers -- plus the error flags); the host
+    // table is built in mg_create, its device copy with the pool
+    MGState LK;
+    void *look_pool;
+    StateRow *look_rows;
+    std::vector<StateRow> look_rows_host;
     // optional per-kernel timing (hipEvents on the launch stream)
     int timing;
     std::vector<hipEvent_t> ev;   // quadruples: before step_kernel, after it, after the auto-reset, after render_kernel
@@ -201,6 +209,27 @@ __global__ void __launch_bounds__(256) reset_copy_kernel(const char *__restrict_
             } else {
                 SH.overflow[e] = S.overflow[e];
             }
+        }
+    }
+}
+
+// every env's rows src -> dst (mg_lookahead: the sim's state into its scratch pool).  One thread per (row, env),
+// envs fastest: a wavefront moves one contiguous segment of a [slot][N] row; a workgroup takes LOOK_ROWS_PER_WG rows
+// of its 256 envs.
+#define LOOK_ROWS_PER_WG 8
+__global__ void __launch_bounds__(256) look_copy_kernel(const char *__restrict__ src, char *__restrict__ dst,
+                                                        const StateRow *__restrict__ rows, int nrows, int n_envs) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_envs) return;
+    const int r0 = blockIdx.y * LOOK_ROWS_PER_WG, r1 = r0 + LOOK_ROWS_PER_WG < nrows ? r0 + LOOK_ROWS_PER_WG : nrows;
+    for (int r = r0; r < r1; r++) {
+        const StateRow w = rows[r];   // uniform over the workgroup
+        const size_t o = w.off + (size_t)e * w.esize;
+        switch (w.esize) {
+        case 8: *(uint64_t *)(dst + o) = *(const uint64_t *)(src + o); break;
+        case 4: *(uint32_t *)(dst + o) = *(const uint32_t *)(src + o); break;
+        case 2: *(uint16_t *)(dst + o) = *(const uint16_t *)(src + o); break;
+        default: dst[o] = src[o]; break;
         }
     }
 }
@@ -457,6 +486,14 @@ int mg_create(const mg_config *cfg, mg_sim **out) {
         s->srows = nullptr; s->snap_stage = s->snap_dev = nullptr; s->ev_snap = nullptr; s->snap_inflight = 0;
         HIPC(hipMalloc((void **)&s->srows, srows.size() * sizeof(SnapRow)));
         HIPC(hipMemcpy(s->srows, srows.data(), srows.size() * sizeof(SnapRow), hipMemcpyHostToDevice));
+    }
+    {   // the rows a lookahead copies into its scratch pool (allocated by the first mg_lookahead)
+        const uint64_t mt0 = (uint64_t)((const char *)s->S.mt_key - (const char *)s->pool);
+        const uint64_t mt1 = (uint64_t)((const char *)s->S.mt_pos - (const char *)s->pool);
+        for (const StateRow &r : rows)
+            if (r.off < mt0 || r.off >= mt1) s->look_rows_host.push_back(r);
+        s->look_rows_host.push_back(StateRow{(uint64_t)((const char *)s->S.overflow - (const char *)s->pool), 4u, 0u});
+        s->look_pool = nullptr; s->look_rows = nullptr;
     }
     std::vector<uint32_t> seeds(cfg->num_envs);
     for (int i = 0; i < cfg->num_envs; i++) seeds[i] = cfg->seeds ? cfg->seeds[i] : cfg->base_seed + (uint32_t)i;
@@ -986,6 +1023,48 @@ int mg_restore(mg_sim *s, const uint8_t *blob, const int32_t *envs, const int32_
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// lookahead (kernel: mg_lookahead.h)
+static int look_alloc(mg_sim *s) {
+    s->LK = s->S;
+    s->LK.target_out = nullptr;   // nothing of a rollout reaches the bound outputs
+    Carver sz = {nullptr, 0};
+    layout(s->LK, sz, false);
+    void *pool = nullptr;
+    hipError_t err = hipMalloc(&pool, sz.off + 256);
+    if (err != hipSuccess) return set_err(-12, std::string("mg_lookahead: hipMalloc scratch pool: ") + hipGetErrorString(err));
+    StateRow *rows = nullptr;
+    const size_t rb = s->look_rows_host.size() * sizeof(StateRow);
+    err = hipMalloc((void **)&rows, rb);
+    if (err == hipSuccess) err = hipMemset(pool, 0, sz.off + 256);
+    if (err == hipSuccess) err = hipMemcpy(rows, s->look_rows_host.data(), rb, hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        (void)hipFree(pool); (void)hipFree(rows);
+        return set_err(-12, std::string("mg_lookahead: scratch pool setup: ") + hipGetErrorString(err));
+    }
+    Carver real = {(char *)pool, 0};
+    layout(s->LK, real, false);
+    s->look_pool = pool; s->look_rows = rows;
+    return 0;
+}
+
+int mg_lookahead(mg_sim *s, const uint8_t *actions, int32_t H, const mg_lookahead_out *out, void *stream) {
+    if (!s || !out || !out->score) return set_err(-22, "mg_lookahead: null sim, out or out->score");
+    if (H < 0 || H > 4096) return set_err(-22, "mg_lookahead: H must be in [0, 4096]");
+    if (!actions && H > 0) return set_err(-22, "mg_lookahead: null actions with H > 0");
+    HIPC(hipSetDevice(s->device));
+    if (!s->look_pool)
+        if (int rc = look_alloc(s)) return rc;
+    hipStream_t st = as_stream(stream);
+    const int nrows = (int)s->look_rows_host.size();
+    hipLaunchKernelGGL(look_copy_kernel, dim3((s->S.n_envs + 255) / 256, (nrows + LOOK_ROWS_PER_WG - 1) / LOOK_ROWS_PER_WG),
+                       dim3(256), 0, st, (const char *)s->pool, (char *)s->look_pool, s->look_rows, nrows, s->S.n_envs);
+    HIPC(hipGetLastError());
+    const LookOut lo = {out->score, out->steps, out->bodies, out->counts, out->errors};
+    HIPC(mg_launch_lookahead(s->LK, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+    return 0;
+}
+
 void mg_destroy(mg_sim *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -1002,6 +1081,7 @@ void mg_destroy(mg_sim *s) {
         (void)hipHostFree(s->snap_stage); (void)hipFree(s->snap_dev);
     }
     (void)hipFree(s->srows);
+    (void)hipFree(s->look_pool); (void)hipFree(s->look_rows);
     (void)hipFree(s->pool);
     (void)hipFree(s->dlib);
     (void)hipFree(s->reset_mask);

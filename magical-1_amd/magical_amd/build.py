@@ -19,6 +19,7 @@ PROF_OUT = os.path.join(HERE, "libmagical_sim_prof.so")  # -DMG_PROFILE phase ti
 _COMMON = ["mg_common.h", "mg_math.h", "mg_state.h", "mg_stepforms.h", "mg_launch.h", "mg_prof.h"]
 _PHYS = _COMMON + ["mg_phys.h", "mg_step.h"]
 _STEP = _PHYS + ["mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h"]
+_LOOK = _STEP + ["mg_lookahead.h"]   # mg_lookahead's kernels: the step kernel's pairs with the env-step loop inside
 UNITS = {  # translation unit -> headers it depends on (one unit per kernel family: they compile in parallel)
     "mg_sim.hip": _COMMON + ["mg_phys.h", "mg_snapshot.h"],
     "mg_snapshot.hip": ["mg_common.h", "mg_snapshot.h"],
@@ -27,6 +28,10 @@ UNITS = {  # translation unit -> headers it depends on (one unit per kernel fami
     "mg_step_v4.hip": _STEP,
     "mg_step_quad.hip": _STEP,
     "mg_step_hbm.hip": _STEP,
+    "mg_lookahead.hip": _COMMON,
+    "mg_look_v4.hip": _LOOK,
+    "mg_look_quad.hip": _LOOK,
+    "mg_look_hbm.hip": _LOOK,
     "mg_raster.hip": _PHYS + ["mg_render.h"],
     "mg_replay.hip": ["mg_common.h"],
 }

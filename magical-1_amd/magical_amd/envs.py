@@ -368,6 +368,41 @@ class VecMagicalEnv:
         ra = None if recs is None else (ctypes.c_int32 * n)(*[int(r) for r in recs])
         native.check(self.lib.mg_restore(self.handle, ctypes.c_void_p(snap.blob.data_ptr()), ea, ra, n, self._stream()))
 
+    # -- lookahead ---------------------------------------------------------------
+    def lookahead(self, actions, bodies=False):
+        """What happens if these envs run these actions -- without touching them (mg_lookahead).  actions: [H, N]
+        uint8 (tensor or array-like; [N] is H = 1; H = 0, an empty [0, N], scores the current states), step h of env e
+        at actions[h, e].  Every env runs min(H, steps left in its episode) env-steps of physics only (no render, no
+        auto-reset) on a scratch copy of its state, bit-identical to as many step() calls, and is then scored.
+        Returns fresh device tensors: 'score' f64[N] (the task's score of the final state; eval_score where the
+        episode ends inside the horizon), 'steps' i32[N] (env-steps simulated), 'errors' i32[N] (errors() as it
+        would stand); with bodies=True also 'bodies' f64[N, 16, 6] and 'counts' i32[N, 4] of the final state, as
+        bodies().  The env itself -- state, RNG, episode phase, frames, outputs -- is unchanged.  Enqueued on the
+        current stream; works with window=True and frames_only outputs."""
+        a = torch.as_tensor(actions)
+        if a.dim() == 1:
+            a = a[None]
+        if a.dim() != 2 or a.shape[1] != self.num_envs:
+            raise ValueError(f"lookahead: actions must be [H, {self.num_envs}], got {tuple(a.shape)}")
+        a = a.to(self.device, torch.uint8).contiguous()
+        n, dev = self.num_envs, self.device
+        res = collections.OrderedDict([("score", torch.empty(n, dtype=torch.float64, device=dev)),
+                                       ("steps", torch.empty(n, dtype=torch.int32, device=dev)),
+                                       ("errors", torch.empty(n, dtype=torch.int32, device=dev))])
+        if bodies:
+            res["bodies"] = torch.empty((n, 16, 6), dtype=torch.float64, device=dev)
+            res["counts"] = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        out = native.mg_lookahead_out(**{k: v.data_ptr() for k, v in res.items()})
+        native.check(self.lib.mg_lookahead(self.handle, ctypes.c_void_p(a.data_ptr()) if a.shape[0] else None,
+                                           int(a.shape[0]), ctypes.byref(out), self._stream()))
+        self._last_lookahead = a   # (alive until the next call: the kernel reads it on the stream)
+        return res
+
+    def score(self):
+        """f64[N]: the task's score (score_on_end_of_traj) of every env's current state, mid-episode or not -- a
+        zero-step lookahead."""
+        return self.lookahead(torch.empty((0, self.num_envs), dtype=torch.uint8))["score"]
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.mg_destroy(self.handle)
@@ -436,6 +471,21 @@ class MagicalEnv:
         d = bool(done[0].item())
         score = float(info["eval_score"][0].item())
         return self._np_obs(obs), float(rew[0].item()), d, {"eval_score": score}
+
+    def score(self):
+        """The task's score (score_on_end_of_traj) of the current state, at any point of the episode; step() reports
+        it as info['eval_score'] only on the step that ends one."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before score()")
+        return float(self._vec.score()[0].item())
+
+    def lookahead(self, actions):
+        """Score of the state after running `actions` (a sequence of action ids, cut at the episode's end) from the
+        current state, which stays as it is: (score, env-steps simulated)."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before lookahead()")
+        res = self._vec.lookahead(torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1))
+        return float(res["score"][0].item()), int(res["steps"][0].item())
 
     def get_state(self):
         """The env's whole state as bytes (a one-record snapshot blob, magical_amd.snapshot): physics, RNG, episode

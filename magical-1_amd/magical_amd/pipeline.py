@@ -214,6 +214,30 @@ class PipelinedVecEnv:
         self._last = []
         return self._obs()
 
+    def lookahead(self, actions, bodies=False):
+        """VecMagicalEnv.lookahead for the whole pool: actions [H, num_envs] ([num_envs]: H = 1); chunk k runs its
+        columns [bounds[k], bounds[k + 1]) on its own stream once every chunk's last step is done, and the results
+        are concatenated in env order (complete: the caller's stream is ordered after the chunks)."""
+        a = torch.as_tensor(actions)
+        if a.dim() == 1:
+            a = a[None]
+        if a.dim() != 2 or a.shape[1] != self.num_envs:
+            raise ValueError(f"lookahead: actions must be [H, {self.num_envs}], got {tuple(a.shape)}")
+        a = a.to(self.device, torch.uint8)
+        self.wait()
+        self._fork()
+        b, parts = self.bounds, []
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            with torch.cuda.stream(st):   # a column slice is strided: the chunk gets its own contiguous [H, m] copy
+                parts.append(sim.lookahead(a[:, b[k]:b[k + 1]].contiguous(), bodies=bodies))
+        self.wait()
+        out = collections.OrderedDict()
+        for key in parts[0]:
+            out[key] = torch.cat([p[key] for p in parts])
+            for p in parts:   # allocated on the chunks' streams, read here on the caller's
+                p[key].record_stream(self._caller())
+        return out
+
     def _obs(self):
         from .envs import window_stack
         allo, ego, past = self.buffers.get("allo"), self.buffers.get("ego"), self.buffers.get("past_obs")
