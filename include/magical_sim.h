@@ -229,6 +229,46 @@ typedef struct {
  * Returns -22 and launches nothing for a null sim / out / out->score, a null actions_dev with H > 0, or H
  * outside [0, 4096]. */
 int mg_lookahead(mg_sim *sim, const uint8_t *actions_dev, int32_t H, const mg_lookahead_out *out, void *stream);
+/* Plan: "which of these K action sequences is best for each env", without touching the envs.  One call fans every
+ * env's state out to K rollouts, runs all K * N of them as one grid and reduces to the best candidate per env on the
+ * device.  Caller-owned device outputs (N = num_envs): */
+#define MG_PLAN_MAX_ROLLOUTS 262144   /* K * num_envs of one call */
+typedef struct {
+    int32_t *best;         /* i32[N]: index k of the env's best candidate: highest score, lowest k on ties; required */
+    double  *best_score;   /* f64[N]: that candidate's score; NULL ok */
+    uint8_t *first_action; /* u8[N]: actions[0][best[e]][e] (H = 0: left unwritten); NULL ok */
+    double  *scores;       /* f64[K][N]: every candidate's score, as mg_lookahead_out.score; NULL ok */
+    int32_t *steps;        /* i32[K][N]: as mg_lookahead_out.steps; NULL ok */
+    int32_t *errors;       /* i32[K][N]: as mg_lookahead_out.errors; NULL ok */
+} mg_plan_out;
+/* actions_dev: device u8[H][K][N], candidate-major within a step: step h of candidate k of env e at (h*K + k)*N + e,
+ * each in [0, 18).  0 <= H <= 4096, 1 <= K <= 4096, K * N <= MG_PLAN_MAX_ROLLOUTS.
+ * Rollout k*N + e starts from env e's current state and is exactly what mg_lookahead computes for env e with the
+ * action column actions[:, k, e]: the same per-env horizon min(H, remaining), the same stop at the terminal step, the
+ * same score, steps and error flags, bit for bit (it is the same kernel, for the (form, envs per workgroup) pair of
+ * mg_step, on a grid of K * N envs).  H = 0 scores the current state K times: best = 0, steps = 0, and actions_dev
+ * may be NULL.
+ * best is the argmax over all K candidates, the lowest k among equal scores (scores are never NaN).  Error flags do
+ * not exclude a candidate: they are reported through `errors` for the caller to act on.
+ * The sim is observationally untouched: state rows, RNG, episode_steps, error flags, frame rings, window rings,
+ * bound outputs, the next-layout shadow and its pending work are unchanged, and a following mg_step gives the
+ * same bytes as if the call had not happened.  It works in every mode (window rings, frames_only outputs,
+ * auto_reset 0 or 1, the unwrapped surface) and touches no frames.
+ * The rollouts run on a fan pool that the sim owns, separate from mg_lookahead's scratch: allocated by the first call
+ * for its K * N rollouts, re-allocated by a later call that needs more (those calls alone synchronise the device),
+ * freed in mg_destroy.  An allocation failure returns -12 and leaves the sim usable, without a fan pool.  Everything
+ * else is enqueued on `stream` with no host sync; two plans in flight on different streams of one handle are not
+ * supported.
+ * Returns -22 and launches nothing for a null sim / out / out->best, a null actions_dev with H > 0, or H, K or
+ * K * N out of range. */
+int mg_plan(mg_sim *sim, const uint8_t *actions_dev, int32_t H, int32_t K, const mg_plan_out *out, void *stream);
+/* Random-shooting candidates for mg_plan: fills actions_dev u8[H][K][N], each action held for repeat >= 1 env-steps.
+ * With J = ceil(H / repeat), row [h][k][:] holds the bytes mg_random_actions(sim, ., key, step + k*J + h/repeat, .)
+ * writes (integer division): candidate k uses the J counter values from step + k*J on, so a decision consumes K*J
+ * of them.  Returns -22 for null arguments, repeat < 1, or H, K or K * N out of mg_plan's range; H = 0 is a no-op
+ * that returns 0. */
+int mg_plan_sample(mg_sim *sim, uint8_t *actions_dev, int32_t H, int32_t K, int32_t repeat, uint64_t key, uint64_t step,
+                   void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

@@ -1,0 +1,110 @@
+// mg_plan.hip -- mg_plan's fan-out copy, best-of-K reduction and candidate sampler (mg_plan.h; the rollouts are the
+// lookahead kernel on the fan pool, the C ABI and the pool live in mg_sim.hip).
+#include "mg_plan.h"
+#include "mg_philox.h"
+
+// Fan-out: a workgroup takes PLAN_ROWS_PER_WG rows of its 256 envs, reads each source element once into registers
+// and stores it K times, envs fastest across lanes -- source traffic does not grow with K, and every store of a
+// wavefront is one contiguous segment of a [slot][Mpad] row.  Rows of 1- and 2-byte elements move as 4-byte words
+// (a lane carries 4 or 2 neighbouring envs, so such a row occupies the workgroup's first 64 or 128 lanes): the source
+// word is always aligned (rows start on 4-byte boundaries and are padded to 64 envs), the destination word of candidate
+// k is when k * n_envs elements are a whole number of words -- every k when n_envs is a multiple of 4 -- and otherwise,
+// or where the word would run past the candidate's last env, the lane stores its elements one by one.
+#define PLAN_ROWS_PER_WG 8
+__global__ void __launch_bounds__(256) plan_fan_kernel(const char *__restrict__ src, char *__restrict__ dst,
+                                                       const PlanRow *__restrict__ rows, int nrows, int n_envs, int K) {
+    const int tid = threadIdx.x, r0 = blockIdx.y * PLAN_ROWS_PER_WG;
+    PlanRow w[PLAN_ROWS_PER_WG];   // uniform over the workgroup
+    uint64_t v[PLAN_ROWS_PER_WG];
+    int e0[PLAN_ROWS_PER_WG];      // the lane's first env of the row; -1: none
+#pragma unroll
+    for (int i = 0; i < PLAN_ROWS_PER_WG; i++) {
+        e0[i] = -1;
+        v[i] = 0;
+        if (r0 + i >= nrows) continue;
+        w[i] = rows[r0 + i];
+        const int pack = w[i].esize >= 4 ? 1 : 4 / (int)w[i].esize;
+        const int e = blockIdx.x * 256 + tid * pack;
+        if (tid * pack >= 256 || e >= n_envs) continue;
+        e0[i] = e;
+        const char *p = src + w[i].src + (size_t)e * w[i].esize;
+        v[i] = w[i].esize == 8 ? *(const uint64_t *)p : (uint64_t)(*(const uint32_t *)p);
+    }
+    for (int k = 0; k < K; k++) {
+        const size_t col = (size_t)k * (size_t)n_envs;
+#pragma unroll
+        for (int i = 0; i < PLAN_ROWS_PER_WG; i++) {
+            if (e0[i] < 0) continue;
+            const uint32_t es = w[i].esize;
+            char *p = dst + w[i].dst + (col + (size_t)e0[i]) * es;
+            if (es == 8) {
+                *(uint64_t *)p = v[i];
+            } else if (es == 4) {
+                *(uint32_t *)p = (uint32_t)v[i];
+            } else {
+                const int pack = 4 / (int)es;
+                if (((col * es) & 3) == 0 && e0[i] + pack <= n_envs) {
+                    *(uint32_t *)p = (uint32_t)v[i];
+                } else {
+                    for (int j = 0; j < pack && e0[i] + j < n_envs; j++) {
+                        if (es == 2) *(uint16_t *)(p + 2 * j) = (uint16_t)(v[i] >> (16 * j));
+                        else p[j] = (char)(uint8_t)(v[i] >> (8 * j));
+                    }
+                }
+            }
+        }
+    }
+}
+
+hipError_t mg_launch_plan_fan(const char *src_pool, char *dst_pool, const PlanRow *rows_dev, int nrows, int n_envs, int K,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(plan_fan_kernel, dim3((n_envs + 255) / 256, (nrows + PLAN_ROWS_PER_WG - 1) / PLAN_ROWS_PER_WG),
+                       dim3(256), 0, st, src_pool, dst_pool, rows_dev, nrows, n_envs, K);
+    return hipGetLastError();
+}
+
+// one thread per env over its K candidates' scores, each read coalesced along e; strict >: the lowest k wins a tie
+// (scores are never NaN)
+__global__ void __launch_bounds__(256) plan_reduce_kernel(const double *__restrict__ scores,
+                                                          const uint8_t *__restrict__ actions, int H, int n_envs, int K,
+                                                          int32_t *__restrict__ best, double *__restrict__ best_score,
+                                                          uint8_t *__restrict__ first_action) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_envs) return;
+    double bs = scores[e];
+    int b = 0;
+    for (int k = 1; k < K; k++) {
+        const double s = scores[(size_t)k * n_envs + e];
+        if (s > bs) { bs = s; b = k; }
+    }
+    best[e] = b;
+    if (best_score) best_score[e] = bs;
+    if (first_action && actions && H > 0) first_action[e] = actions[(size_t)b * n_envs + e];   // step 0 of candidate b
+}
+
+hipError_t mg_launch_plan_reduce(const double *scores, const uint8_t *actions, int H, int n_envs, int K, int32_t *best,
+                                 double *best_score, uint8_t *first_action, hipStream_t st) {
+    hipLaunchKernelGGL(plan_reduce_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, st, scores, actions, H, n_envs, K,
+                       best, best_score, first_action);
+    return hipGetLastError();
+}
+
+// one thread per action byte of u8[H][K][n_envs], envs fastest
+__global__ void __launch_bounds__(256) plan_sample_kernel(uint8_t *__restrict__ out, int n_envs, int H, int K, int repeat,
+                                                          uint64_t key, uint64_t step) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)H * K * n_envs) return;
+    const int e = (int)(i % (uint64_t)n_envs);
+    const uint64_t hk = i / (uint64_t)n_envs;
+    const uint64_t h = hk / (uint64_t)K, k = hk % (uint64_t)K;
+    const uint64_t J = ((uint64_t)H + repeat - 1) / repeat;
+    out[i] = philox_action(key, step + k * J + h / (uint64_t)repeat, e);
+}
+
+hipError_t mg_launch_plan_sample(uint8_t *out, int n_envs, int H, int K, int repeat, uint64_t key, uint64_t step,
+                                 hipStream_t st) {
+    const uint64_t total = (uint64_t)H * K * n_envs;   // <= 4096 * MG_PLAN_MAX_ROLLOUTS = 2^30
+    hipLaunchKernelGGL(plan_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, n_envs, H, K,
+                       repeat, key, step);
+    return hipGetLastError();
+}

@@ -15,6 +15,8 @@
 #include "../../include/magical_sim.h"
 #include "mg_launch.h"
 #include "mg_phys.h"
+#include "mg_philox.h"
+#include "mg_plan.h"
 #include "mg_snapshot.h"
 
 static thread_local std::string g_err;
@@ -85,6 +87,16 @@ struct mg_sim {
     void *look_pool;
     StateRow *look_rows;
     std::vector<StateRow> look_rows_host;
+    // plan (mg_plan): FP is the fan pool, a state of plan_cap >= K * num_envs rollout envs laid out as LK is (no frame
+    // rings); rollout k * num_envs + e starts as a copy of env e.  One allocation (plan_pool) holds the state rows,
+    // the rollouts' scores (plan_scores f64[plan_cap]: the reduction's input also when the caller wants no scores) and
+    // the device table of the fan-out's rows (plan_rows: look_rows_host's rows with their place in FP).  Allocated by
+    // the first call, re-allocated by a call that needs more rollouts
+    MGState FP;
+    void *plan_pool;
+    int plan_cap;
+    double *plan_scores;
+    PlanRow *plan_rows;
     // optional per-kernel timing (hipEvents on the launch stream)
     int timing;
     std::vector<hipEvent_t> ev;   // quadruples: before step_kernel, after it, after the auto-reset, after render_kernel
@@ -150,26 +162,11 @@ __global__ void __launch_bounds__(256) sincos_kernel(const double *x, double *s,
     mg_sincos(x[i], s[i], c[i]);
 }
 
-// Philox4x32-10 (Salmon et al. 2011): counter = (step lo, step hi, env, 0), key = (k lo, k hi)
-__device__ __forceinline__ uint32_t mulhilo(uint32_t a, uint32_t b, uint32_t &hi) {
-    uint64_t p = (uint64_t)a * b;
-    hi = (uint32_t)(p >> 32);
-    return (uint32_t)p;
-}
+// uniform random actions (Philox4x32-10: mg_philox.h)
 __global__ void __launch_bounds__(256) actions_kernel(uint8_t *out, int n, uint64_t key, uint64_t step) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    uint32_t c0 = (uint32_t)step, c1 = (uint32_t)(step >> 32), c2 = (uint32_t)e, c3 = 0;
-    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-    for (int r = 0; r < 10; r++) {
-        uint32_t hi0, hi1;
-        uint32_t lo0 = mulhilo(0xD2511F53u, c0, hi0);
-        uint32_t lo1 = mulhilo(0xCD9E8D57u, c2, hi1);
-        uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[e] = (uint8_t)(c0 % 18u);
+    out[e] = philox_action(key, step, e);
 }
 
 // env e's per-env state rows src -> dst for the envs in mask (pend[e] = mask[e] for every env): the
@@ -494,6 +491,7 @@ int mg_create(const mg_config *cfg, mg_sim **out) {
             if (r.off < mt0 || r.off >= mt1) s->look_rows_host.push_back(r);
         s->look_rows_host.push_back(StateRow{(uint64_t)((const char *)s->S.overflow - (const char *)s->pool), 4u, 0u});
         s->look_pool = nullptr; s->look_rows = nullptr;
+        s->plan_pool = nullptr; s->plan_cap = 0; s->plan_scores = nullptr; s->plan_rows = nullptr;
     }
     std::vector<uint32_t> seeds(cfg->num_envs);
     for (int i = 0; i < cfg->num_envs; i++) seeds[i] = cfg->seeds ? cfg->seeds[i] : cfg->base_seed + (uint32_t)i;
@@ -1065,6 +1063,105 @@ int mg_lookahead(mg_sim *s, const uint8_t *actions, int32_t H, const mg_lookahea
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// plan (kernels: mg_plan.hip; the rollouts: the lookahead kernel on the fan pool)
+static int plan_check_sizes(const mg_sim *s, const char *fn, int32_t H, int32_t K) {
+    if (H < 0 || H > 4096) return set_err(-22, std::string(fn) + ": H must be in [0, 4096]");
+    if (K < 1 || K > 4096) return set_err(-22, std::string(fn) + ": K must be in [1, 4096]");
+    if ((int64_t)K * s->S.n_envs > MG_PLAN_MAX_ROLLOUTS)
+        return set_err(-22, std::string(fn) + ": K * num_envs = " + std::to_string((int64_t)K * s->S.n_envs) +
+                                " rollouts, more than MG_PLAN_MAX_ROLLOUTS = " + std::to_string(MG_PLAN_MAX_ROLLOUTS));
+    return 0;
+}
+
+// (re)allocate the fan pool for M rollouts.  The device is synchronised first: an earlier call's kernels may still be
+// running on the pool that is freed here.  On failure the sim has no fan pool and stays usable (the next mg_plan
+// allocates again)
+static int plan_alloc(mg_sim *s, int M) {
+    HIPC(hipDeviceSynchronize());
+    (void)hipFree(s->plan_pool);
+    s->plan_pool = nullptr; s->plan_cap = 0; s->plan_scores = nullptr; s->plan_rows = nullptr;
+    MGState F = s->S;
+    F.target_out = nullptr;   // nothing of a rollout reaches the bound outputs
+    F.N = (M + 63) / 64 * 64;
+    const size_t nrows = s->look_rows_host.size();
+    auto carve = [&](char *base, std::vector<StateRow> *rows, double **scores, PlanRow **table) {
+        Carver c = {base, 0};
+        c.rows = rows;
+        layout(F, c, false);
+        *scores = c.take<double>((size_t)F.N);
+        *table = c.take<PlanRow>(nrows);
+        return c.off + 256;
+    };
+    double *scores = nullptr;
+    PlanRow *table = nullptr;
+    const size_t bytes = carve(nullptr, nullptr, &scores, &table);
+    void *pool = nullptr;
+    hipError_t err = hipMalloc(&pool, bytes);
+    if (err != hipSuccess)
+        return set_err(-12, std::string("mg_plan: hipMalloc fan pool of ") + std::to_string(bytes) + " bytes for " +
+                                std::to_string(M) + " rollouts: " + hipGetErrorString(err));
+    std::vector<StateRow> rows;
+    carve((char *)pool, &rows, &scores, &table);
+    // the fan-out's rows: look_rows_host's choice (every state row but the MT19937 key, then the error flags) of the
+    // fan pool's rows, which layout() lists in the same order as the sim's
+    std::vector<PlanRow> pr;
+    const uint64_t mt0 = (uint64_t)((const char *)F.mt_key - (const char *)pool);
+    const uint64_t mt1 = (uint64_t)((const char *)F.mt_pos - (const char *)pool);
+    for (const StateRow &r : rows)
+        if (r.off < mt0 || r.off >= mt1) pr.push_back(PlanRow{0u, r.off, r.esize, 0u});
+    pr.push_back(PlanRow{0u, (uint64_t)((const char *)F.overflow - (const char *)pool), 4u, 0u});
+    bool same = pr.size() == nrows;
+    for (size_t i = 0; same && i < nrows; i++) {
+        pr[i].src = s->look_rows_host[i].off;
+        same = pr[i].esize == s->look_rows_host[i].esize;
+    }
+    if (!same) {
+        (void)hipFree(pool);
+        return set_err(-5, "mg_plan: the fan pool's rows do not match the sim's (layout() changed?)");
+    }
+    err = hipMemset(pool, 0, bytes);
+    if (err == hipSuccess) err = hipMemcpy(table, pr.data(), nrows * sizeof(PlanRow), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        (void)hipFree(pool);
+        return set_err(-12, std::string("mg_plan: fan pool setup: ") + hipGetErrorString(err));
+    }
+    s->FP = F;
+    s->plan_pool = pool; s->plan_cap = M; s->plan_scores = scores; s->plan_rows = table;
+    return 0;
+}
+
+int mg_plan(mg_sim *s, const uint8_t *actions, int32_t H, int32_t K, const mg_plan_out *out, void *stream) {
+    if (!s || !out || !out->best) return set_err(-22, "mg_plan: null sim, out or out->best");
+    if (int rc = plan_check_sizes(s, "mg_plan", H, K)) return rc;
+    if (!actions && H > 0) return set_err(-22, "mg_plan: null actions with H > 0");
+    HIPC(hipSetDevice(s->device));
+    const int n = s->S.n_envs, M = K * n;
+    if (M > s->plan_cap)
+        if (int rc = plan_alloc(s, M)) return rc;
+    hipStream_t st = as_stream(stream);
+    // the pool may be larger than this call needs: its rows keep the stride it was laid out with, the launch covers M
+    MGState F = s->FP;
+    F.n_envs = M;
+    HIPC(mg_launch_plan_fan((const char *)s->pool, (char *)s->plan_pool, s->plan_rows, (int)s->look_rows_host.size(), n, K, st));
+    double *scores = out->scores ? out->scores : s->plan_scores;
+    const LookOut lo = {scores, out->steps, nullptr, nullptr, out->errors};
+    HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+    HIPC(mg_launch_plan_reduce(scores, actions, H, n, K, out->best, out->best_score, out->first_action, st));
+    return 0;
+}
+
+int mg_plan_sample(mg_sim *s, uint8_t *actions, int32_t H, int32_t K, int32_t repeat, uint64_t key, uint64_t step,
+                   void *stream) {
+    if (!s || !actions) return set_err(-22, "mg_plan_sample: null argument");
+    if (repeat < 1) return set_err(-22, "mg_plan_sample: repeat must be at least 1");
+    if (int rc = plan_check_sizes(s, "mg_plan_sample", H, K)) return rc;
+    if (H == 0) return 0;
+    HIPC(hipSetDevice(s->device));
+    HIPC(mg_launch_plan_sample(actions, s->S.n_envs, H, K, repeat, key, step, as_stream(stream)));
+    return 0;
+}
+
 void mg_destroy(mg_sim *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -1082,6 +1179,7 @@ void mg_destroy(mg_sim *s) {
     }
     (void)hipFree(s->srows);
     (void)hipFree(s->look_pool); (void)hipFree(s->look_rows);
+    (void)hipFree(s->plan_pool);
     (void)hipFree(s->pool);
     (void)hipFree(s->dlib);
     (void)hipFree(s->reset_mask);

@@ -81,6 +81,21 @@ def observation_space(spec):
     return spaces.Dict(collections.OrderedDict(items))
 
 
+def plan_actions(actions, num_envs):
+    """plan()'s candidate actions as a uint8 [H, K, num_envs] tensor ([K, num_envs] is H = 1), on the device they came
+    on; ValueError for any other shape, no candidate at all, or more rollouts than one mg_plan call takes."""
+    a = torch.as_tensor(actions)
+    if a.dim() == 2:
+        a = a[None]
+    if a.dim() != 3 or a.shape[2] != num_envs:
+        raise ValueError(f"plan: actions must be [H, K, {num_envs}], got {tuple(a.shape)}")
+    if a.shape[1] < 1:
+        raise ValueError("plan: at least one candidate per env (K >= 1)")
+    if a.shape[1] * num_envs > native.PLAN_MAX_ROLLOUTS:
+        raise ValueError(f"plan: K * num_envs = {a.shape[1] * num_envs} rollouts, more than {native.PLAN_MAX_ROLLOUTS}")
+    return a.to(torch.uint8)
+
+
 class VecMagicalEnv:
     """Batched MAGICAL env on one MI355X (C ABI: include/magical_sim.h)."""
 
@@ -403,6 +418,47 @@ class VecMagicalEnv:
         zero-step lookahead."""
         return self.lookahead(torch.empty((0, self.num_envs), dtype=torch.uint8))["score"]
 
+    # -- planning ----------------------------------------------------------------
+    def plan(self, actions, details=False):
+        """Which of K candidate action sequences is best for each env -- without touching the envs (mg_plan).
+        actions: [H, K, N] uint8 (tensor or array-like; [K, N] is H = 1; an empty [0, K, N] scores the current states K
+        times), step h of candidate k of env e at actions[h, k, e].  Candidate k of env e is exactly
+        lookahead(actions[:, k])[e]; all K * N rollouts run as one grid on a fan pool the sim owns.  Returns fresh
+        device tensors: 'best' i32[N] (the candidate with the highest score, the lowest k on ties), 'best_score'
+        f64[N], 'first_action' u8[N] (actions[0, best[e], e]; zeros when H = 0); with details=True also 'scores'
+        f64[K, N], 'steps' i32[K, N] and 'errors' i32[K, N] as lookahead's.  Error flags do not exclude a candidate.
+        Enqueued on the current stream, except that a call needing a larger fan pool than the last allocates it and
+        synchronises the device."""
+        a = plan_actions(actions, self.num_envs).to(self.device).contiguous()
+        H, K, n, dev = int(a.shape[0]), int(a.shape[1]), self.num_envs, self.device
+        res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
+                                       ("best_score", torch.empty(n, dtype=torch.float64, device=dev)),
+                                       ("first_action", torch.zeros(n, dtype=torch.uint8, device=dev))])
+        if details:
+            res["scores"] = torch.empty((K, n), dtype=torch.float64, device=dev)
+            res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+            res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+        out = native.mg_plan_out(**{k: v.data_ptr() for k, v in res.items()})
+        native.check(self.lib.mg_plan(self.handle, ctypes.c_void_p(a.data_ptr()) if H else None, H, K, ctypes.byref(out),
+                                      self._stream()))
+        self._last_plan = a   # (alive until the next call: the kernels read it on the stream)
+        return res
+
+    def sample_plans(self, H, K, repeat=1, key=42, step=0, out=None):
+        """u8[H, K, N] random-shooting candidates for plan() (mg_plan_sample): every action is held for `repeat`
+        env-steps, and with J = ceil(H / repeat) the row [h, k] equals random_actions(step + k * J + h // repeat, key)."""
+        H, K = int(H), int(K)
+        if out is None:
+            out = torch.empty((max(H, 0), max(K, 0), self.num_envs), dtype=torch.uint8, device=self.device)
+        if (tuple(out.shape) != (H, K, self.num_envs) or out.dtype != torch.uint8 or out.device != self.device
+                or not out.is_contiguous()):
+            raise ValueError(f"sample_plans: out must be a contiguous uint8 [{H}, {K}, {self.num_envs}] tensor on {self.device}")
+        # (H = 0: the call checks K and repeat and writes nothing, but refuses a null pointer)
+        buf = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=self.device)
+        native.check(self.lib.mg_plan_sample(self.handle, ctypes.c_void_p(buf.data_ptr()), H, K, int(repeat), int(key),
+                                             int(step), self._stream()))
+        return out
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.mg_destroy(self.handle)
@@ -486,6 +542,18 @@ class MagicalEnv:
             raise RuntimeError("call reset() before lookahead()")
         res = self._vec.lookahead(torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1))
         return float(res["score"][0].item()), int(res["steps"][0].item())
+
+    def plan(self, actions):
+        """The best of K candidate action sequences from the current state, which stays as it is.  actions: [H, K]
+        action ids (candidate k is the column actions[:, k]).  Returns (best, best_score, scores): the index of the
+        highest-scoring candidate (the lowest on ties), its score, and every candidate's score as a float64 array [K]."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before plan()")
+        a = torch.as_tensor(np.asarray(actions), dtype=torch.uint8)
+        if a.dim() != 2:
+            raise ValueError(f"plan: actions must be [H, K], got {tuple(a.shape)}")
+        res = self._vec.plan(a[:, :, None], details=True)
+        return int(res["best"][0].item()), float(res["best_score"][0].item()), res["scores"][:, 0].cpu().numpy()
 
     def get_state(self):
         """The env's whole state as bytes (a one-record snapshot blob, magical_amd.snapshot): physics, RNG, episode

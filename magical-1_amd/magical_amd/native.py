@@ -15,7 +15,9 @@ if os.environ.get("MAGICAL_AMD_EXP_LIB"):   # A/B kernel experiments (tools/gpu_
 EXPORTS = ["mg_create", "mg_bind_outputs", "mg_reset", "mg_step", "mg_render_full", "mg_get_bodies", "mg_get_arbiters",
            "mg_set_body_pose", "mg_get_errors", "mg_seed", "mg_random_actions", "mg_num_envs", "mg_step_form", "mg_enable_timing", "mg_read_timing",
            "mg_set_episode_steps", "mg_selftest_sincos", "mg_replay_lores", "mg_restack", "mg_restack_window", "mg_bind_window",
-           "mg_window_start", "mg_snapshot_bytes", "mg_snapshot", "mg_restore", "mg_lookahead", "mg_destroy", "mg_last_error"]
+           "mg_window_start", "mg_snapshot_bytes", "mg_snapshot", "mg_restore", "mg_lookahead", "mg_plan", "mg_plan_sample",
+           "mg_destroy", "mg_last_error"]
+PLAN_MAX_ROLLOUTS = 262144   # MG_PLAN_MAX_ROLLOUTS: K * num_envs of one mg_plan call
 
 
 class mg_config(ctypes.Structure):
@@ -35,6 +37,11 @@ class mg_buffers(ctypes.Structure):
 class mg_lookahead_out(ctypes.Structure):
     _fields_ = [("score", ctypes.c_void_p), ("steps", ctypes.c_void_p), ("bodies", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p), ("errors", ctypes.c_void_p)]
+
+
+class mg_plan_out(ctypes.Structure):
+    _fields_ = [("best", ctypes.c_void_p), ("best_score", ctypes.c_void_p), ("first_action", ctypes.c_void_p),
+                ("scores", ctypes.c_void_p), ("steps", ctypes.c_void_p), ("errors", ctypes.c_void_p)]
 
 
 class NativeError(RuntimeError):
@@ -97,6 +104,8 @@ def load():
     lib.mg_snapshot.argtypes = [vp, ctypes.POINTER(i32), i32, vp, vp]
     lib.mg_restore.argtypes = [vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp]
     lib.mg_lookahead.argtypes = [vp, vp, i32, ctypes.POINTER(mg_lookahead_out), vp]
+    lib.mg_plan.argtypes = [vp, vp, i32, i32, ctypes.POINTER(mg_plan_out), vp]
+    lib.mg_plan_sample.argtypes = [vp, vp, i32, i32, i32, u64, u64, vp]
     lib.mg_destroy.argtypes = [vp]
     lib.mg_destroy.restype = None
     lib.mg_last_error.restype = ctypes.c_char_p

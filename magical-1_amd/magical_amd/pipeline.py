@@ -238,6 +238,40 @@ class PipelinedVecEnv:
                 p[key].record_stream(self._caller())
         return out
 
+    def plan(self, actions, details=False):
+        """VecMagicalEnv.plan for the whole pool: actions [H, K, num_envs] ([K, num_envs]: H = 1); chunk k plans its
+        envs [bounds[k], bounds[k + 1]) on its own stream once every chunk's last step is done, and the results are
+        concatenated in env order (complete: the caller's stream is ordered after the chunks)."""
+        from .envs import plan_actions
+        a = plan_actions(actions, self.num_envs).to(self.device)
+        self.wait()
+        self._fork()
+        b, parts = self.bounds, []
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            with torch.cuda.stream(st):   # an env slice is strided: the chunk gets its own contiguous [H, K, m] copy
+                parts.append(sim.plan(a[:, :, b[k]:b[k + 1]].contiguous(), details=details))
+        self.wait()
+        out = collections.OrderedDict()
+        for key in parts[0]:
+            out[key] = torch.cat([p[key] for p in parts], dim=-1)   # envs are the last axis of every result
+            for p in parts:   # allocated on the chunks' streams, read here on the caller's
+                p[key].record_stream(self._caller())
+        return out
+
+    def sample_plans(self, H, K, repeat=1, key=42, step=0, out=None):
+        """u8[H, K, num_envs] random-shooting candidates (VecMagicalEnv.sample_plans per chunk).  Chunk k draws with
+        key + k and numbers its envs from 0, as random_actions does: with J = ceil(H / repeat), the row [h, k] equals
+        this pool's random_actions(step + k * J + h // repeat, key)."""
+        H, K = int(H), int(K)
+        if out is None:
+            out = torch.empty((max(H, 0), max(K, 0), self.num_envs), dtype=torch.uint8, device=self.device)
+        if tuple(out.shape) != (H, K, self.num_envs) or out.dtype != torch.uint8 or out.device != self.device:
+            raise ValueError(f"sample_plans: out must be a uint8 [{H}, {K}, {self.num_envs}] tensor on {self.device}")
+        b = self.bounds
+        for k, sim in enumerate(self.sims):   # (on the caller's stream, as random_actions)
+            out[:, :, b[k]:b[k + 1]] = sim.sample_plans(H, K, repeat=repeat, key=key + k, step=step)
+        return out
+
     def _obs(self):
         from .envs import window_stack
         allo, ego, past = self.buffers.get("allo"), self.buffers.get("ego"), self.buffers.get("past_obs")
