@@ -306,6 +306,16 @@ class PipelinedVecEnv:
             sim.set_episode_steps(s[self.bounds[k]:self.bounds[k + 1]])
         self._fork()
 
+    def set_body_pose(self, env, body, x, y, angle):
+        """VecMagicalEnv.set_body_pose for env `env` of the pool: forwarded to its chunk (parity tests)."""
+        env = int(env)
+        if env < 0 or env >= self.num_envs:
+            raise ValueError(f"set_body_pose: env {env} of {self.num_envs}")
+        k = max(c for c in range(self.chunks) if self.bounds[c] <= env)
+        self.wait()
+        self.sims[k].set_body_pose(env - self.bounds[k], body, x, y, angle)
+        self._fork()
+
     def errors(self):
         self.wait()
         return torch.cat([sim.errors() for sim in self.sims])

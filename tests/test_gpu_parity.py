@@ -117,7 +117,9 @@ def test_rollout_parity(name, n, steps):
 # every compiled step-kernel (and render-class) form, forced through the experiment switches read at mg_create
 # (MG_STEP_VARIANT: 0 = HBM state (the default for scenes beyond the LDS caps), 5/6 = compile-time
 # constraint lists with 4 lanes per env (robot scenes), 4 = LDS with runtime lists, one env per 64-lane
-# wavefront (every other scene); MG_STEP_BLK / MG_STEP_BLK0: envs per workgroup)
+# wavefront (every other scene); MG_STEP_BLK / MG_STEP_BLK0: envs per workgroup).  The robot-scene rows are
+# effectively contact-free (45 random steps from reset; live arbiters in 0.16% of MoveToRegion env-steps, DESIGN.md
+# section 2): the forms' contact paths are compared with the oracle in tests/test_contact_forms.py
 KERNEL_FORMS = [
     ("MoveToRegion-Demo-LoRes4E-v0", 70, 45, {"MG_STEP_VARIANT": "0", "MG_STEP_BLK0": "8"}),
     # 4 lanes per env (16 envs per 64-lane workgroup; 70 envs leave shadow lanes in the last one)

@@ -561,6 +561,52 @@ def _twin_layout(kinds, types, poses, rs, robot_first=True):
     return out
 
 
+def new_seen():
+    """what the compared arbiters covered: a case that exercises nothing must not pass"""
+    return dict(arbiters=0, two=0, one=0, wall=0, block_block=0, robot=0)
+
+
+def count_arbiter(w, rob, seen):
+    """one oracle arbiter row `w` of an env whose robot bodies are `rob`, added to `seen`"""
+    seen["arbiters"] += 1
+    seen["two" if int(w[2]) == 2 else "one"] += 1
+    ba, bb = int(w[3]), int(w[4])
+    seen["wall"] += ba < 0 or bb < 0
+    seen["robot"] += (ba in rob) != (bb in rob)
+    seen["block_block"] += ba >= 0 and bb >= 0 and ba not in rob and bb not in rob
+
+
+def gpu_tables(vec):
+    """(bodies, counts, arbiters, contact hashes) of every env of `vec`, as numpy"""
+    bodies, counts = vec.bodies()
+    arbs, hs = vec.arbiters()
+    return bodies.cpu().numpy(), counts.cpu().numpy(), arbs.cpu().numpy(), hs.cpu().numpy()
+
+
+def oracle_tables(o):
+    """(bodies, arbiters, contact hashes) of one oracle env"""
+    return (o.bodies(),) + o.arbiters()
+
+
+def assert_twin_step(t, got, want, rob, seen):
+    """The twin's comparison after step `t`: `got` = gpu_tables(vec), `want` = oracle_tables() of env 0, 1, ... in
+    order, rob[i] the robot bodies of env i.  Bodies within 1e-9, arbiter counts equal, every arbiter's five
+    integer fields equal, its contact fields within 1e-9 and its feature hashes equal; what was compared is
+    counted into `seen`."""
+    bodies, counts, arbs, hs = got
+    for i, (b, ra, rh) in enumerate(want):
+        assert np.abs(bodies[i, :len(b)] - b).max() <= 1e-9, f"step {t} env {i} bodies"
+        na = len(ra)
+        assert counts[i, 3] == na, f"step {t} env {i}: {counts[i, 3]} arbiters vs {na}"
+        for k in range(na):
+            g, w = arbs[i, k], ra[k]
+            assert np.array_equal(g[:5], w[:5]), f"step {t} env {i} arbiter {k}: {g[:5]} vs {w[:5]}"
+            cnt = int(w[2])
+            assert np.abs(g[5:8 + 10 * cnt] - w[5:8 + 10 * cnt]).max() <= 1e-9, f"step {t} env {i} arbiter {k}"
+            assert np.array_equal(hs[i, k, :cnt], rh[k, :cnt]), f"step {t} env {i} arbiter {k} hashes"
+            count_arbiter(w, rob[i], seen)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,n,env", TWIN, ids=[t[0].split("-")[0] + "".join(f"-{k}{v}" for k, v in t[2].items())
                                                    for t in TWIN])
@@ -595,32 +641,13 @@ def test_gpu_narrowphase_twin(name, n, env, monkeypatch):
         orc.append(o)
     acts = np.random.RandomState(5).randint(0, 18, (6, n))
     e0 = epa_runs()
-    seen = dict(arbiters=0, two=0, one=0, wall=0, block_block=0, robot=0)
+    seen = new_seen()
     for t in range(6):
         vec.step(torch.as_tensor(acts[t], dtype=torch.uint8))
-        bodies, counts = vec.bodies()
-        arbs, hs = vec.arbiters()
-        bodies, counts, arbs, hs = bodies.cpu().numpy(), counts.cpu().numpy(), arbs.cpu().numpy(), hs.cpu().numpy()
+        got = gpu_tables(vec)
         for i in range(n):
-            o = orc[i]
-            o.step(int(acts[t, i]))
-            b = o.bodies()
-            assert np.abs(bodies[i, :len(b)] - b).max() <= 1e-9, f"step {t} env {i} bodies"
-            ra, rh = o.arbiters()
-            na = len(ra)
-            assert counts[i, 3] == na, f"step {t} env {i}: {counts[i, 3]} arbiters vs {na}"
-            for k in range(na):
-                g, w = arbs[i, k], ra[k]
-                assert np.array_equal(g[:5], w[:5]), f"step {t} env {i} arbiter {k}: {g[:5]} vs {w[:5]}"
-                cnt = int(w[2])
-                assert np.abs(g[5:8 + 10 * cnt] - w[5:8 + 10 * cnt]).max() <= 1e-9, f"step {t} env {i} arbiter {k}"
-                assert np.array_equal(hs[i, k, :cnt], rh[k, :cnt]), f"step {t} env {i} arbiter {k} hashes"
-                seen["arbiters"] += 1
-                seen["two" if cnt == 2 else "one"] += 1
-                ba, bb = int(w[3]), int(w[4])
-                seen["wall"] += ba < 0 or bb < 0
-                seen["robot"] += (ba in rob[i]) != (bb in rob[i])
-                seen["block_block"] += ba >= 0 and bb >= 0 and ba not in rob[i] and bb not in rob[i]
+            orc[i].step(int(acts[t, i]))
+        assert_twin_step(t, got, [oracle_tables(o) for o in orc], rob, seen)
     need = [k for k in seen if k != "block_block" or spec.task != "MoveToCorner"]   # MoveToCorner: one block
     assert min(seen[k] for k in need) > 0 and seen["arbiters"] >= 2 * n, seen
     assert epa_runs() > e0, "no configuration took the EPA path"
