@@ -269,6 +269,47 @@ int mg_plan(mg_sim *sim, const uint8_t *actions_dev, int32_t H, int32_t K, const
  * that returns 0. */
 int mg_plan_sample(mg_sim *sim, uint8_t *actions_dev, int32_t H, int32_t K, int32_t repeat, uint64_t key, uint64_t step,
                    void *stream);
+/* Cross-entropy planning: `iters` rounds of "draw K candidates, roll them out, refit the sampler to the E best",
+ * iterated on the device.  Everything but the rollouts is integer arithmetic.  With J = ceil(H / repeat) held-action
+ * slots, the sampler is weights_dev, u16[J][18][N]: slot j, action a, env e at (j*18 + a)*N + e, a per-env, per-slot
+ * categorical over the 18 actions held as counts.
+ * Draw D(w_j, c, e): word = the first Philox4x32-10 output word for `key` and counter (c lo, c hi, e, 0) -- the word
+ * mg_random_actions reduces mod 18 --, T = the sum of w_j[0..17][e], r = word % T, the action is the smallest a whose
+ * cumulative weight w_j[0] + .. + w_j[a] exceeds r.  T = 0 (possible only in caller-supplied weights) draws as if all
+ * weights were 1.  (The bias of the modulo is below T / 2^32 < 6e-6 per action.)
+ * Iteration i's candidates: row [h][k][:] = D(w_{h/repeat}, step + (i*K + k)*J + h/repeat, e); with all weights 1,
+ * iteration 0 is byte for byte mg_plan_sample(H, K, repeat, key, step).  A call consumes iters*K*J counter values.  In
+ * iterations i >= 1 candidate 0 is the incumbent instead: column best[e] of the previous iteration's candidates,
+ * copied unchanged, so the best score never decreases and the overall best is among the last candidates.
+ * Every iteration is exactly mg_plan on its candidates (fan-out, the rollout grid, the best-of-K reduction).  Its
+ * elites are the `elites` candidates of an env with the highest scores, the lower k first among equal scores, and
+ * the refit is w[j][a][e] = alpha + the number of elites whose slot-j action (row j*repeat) is a.  It runs after
+ * every iteration, the last included: the weights left behind describe the last elites and can warm-start the next
+ * decision.  Caller-owned device outputs (N = num_envs): */
+typedef struct {
+    int32_t *best;         /* i32[N]: index into the LAST iteration's candidates; required */
+    double  *best_score;   /* f64[N]; NULL ok */
+    uint8_t *first_action; /* u8[N]; NULL ok */
+    double  *scores;       /* f64[K][N] of the last iteration; NULL ok */
+    int32_t *steps;        /* i32[K][N] of the last iteration; NULL ok */
+    int32_t *errors;       /* i32[K][N] of the last iteration; NULL ok */
+    double  *iter_best;    /* f64[iters][N]: best score of every iteration; NULL ok */
+} mg_plan_cem_out;
+/* actions_dev: device u8[H][K][N], a workspace laid out as mg_plan's candidates; on return the last iteration's
+ * candidates.  weights_dev: device u16[J][18][N], in/out; warm = 0 starts from all-ones weights (the buffer's
+ * contents are not read), warm = 1 from weights_dev as it is.  Both are the caller's: the library allocates neither.
+ * 1 <= H <= 4096, K and K * N as for mg_plan, 1 <= iters <= 64, 1 <= elites <= K, 0 <= alpha <= 1024, repeat >= 1.
+ * The sim is observationally untouched: state rows, RNG, episode_steps, error flags, frame rings, window rings,
+ * bound outputs, the next-layout shadow and its pending work are unchanged, and a following mg_step gives the
+ * same bytes as if the call had not happened.  It works in every mode mg_plan does and touches no frames.
+ * The rollouts run on mg_plan's fan pool, which also holds the per-env elite threshold the kernels pass between
+ * them; the pool is (re)allocated as in mg_plan (those calls alone synchronise the device).  Everything else,
+ * every iteration included, is enqueued on `stream` with no host sync.
+ * Returns -22 and launches nothing for a null sim / actions_dev / weights_dev / out / out->best, or any argument
+ * outside the ranges above (warm other than 0 or 1 included). */
+int mg_plan_cem(mg_sim *sim, uint8_t *actions_dev, uint16_t *weights_dev, int32_t warm,
+                int32_t H, int32_t K, int32_t iters, int32_t elites, int32_t alpha, int32_t repeat,
+                uint64_t key, uint64_t step, const mg_plan_cem_out *out, void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

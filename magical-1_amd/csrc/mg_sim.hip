@@ -17,6 +17,7 @@
 #include "mg_phys.h"
 #include "mg_philox.h"
 #include "mg_plan.h"
+#include "mg_cem.h"
 #include "mg_snapshot.h"
 
 static thread_local std::string g_err;
@@ -91,12 +92,15 @@ struct mg_sim {
     // rings); rollout k * num_envs + e starts as a copy of env e.  One allocation (plan_pool) holds the state rows,
     // the rollouts' scores (plan_scores f64[plan_cap]: the reduction's input also when the caller wants no scores) and
     // the device table of the fan-out's rows (plan_rows: look_rows_host's rows with their place in FP).  Allocated by
-    // the first call, re-allocated by a call that needs more rollouts
+    // the first call, re-allocated by a call that needs more rollouts.  mg_plan_cem's per-env scratch, the elite
+    // threshold (cem_thr f64[num_envs], cem_kthr i32[num_envs]), is part of the same allocation
     MGState FP;
     void *plan_pool;
     int plan_cap;
     double *plan_scores;
     PlanRow *plan_rows;
+    double *cem_thr;
+    int32_t *cem_kthr;
     // optional per-kernel timing (hipEvents on the launch stream)
     int timing;
     std::vector<hipEvent_t> ev;   // quadruples: before step_kernel, after it, after the auto-reset, after render_kernel
@@ -492,6 +496,7 @@ int mg_create(const mg_config *cfg, mg_sim **out) {
         s->look_rows_host.push_back(StateRow{(uint64_t)((const char *)s->S.overflow - (const char *)s->pool), 4u, 0u});
         s->look_pool = nullptr; s->look_rows = nullptr;
         s->plan_pool = nullptr; s->plan_cap = 0; s->plan_scores = nullptr; s->plan_rows = nullptr;
+        s->cem_thr = nullptr; s->cem_kthr = nullptr;
     }
     std::vector<uint32_t> seeds(cfg->num_envs);
     for (int i = 0; i < cfg->num_envs; i++) seeds[i] = cfg->seeds ? cfg->seeds[i] : cfg->base_seed + (uint32_t)i;
@@ -1081,16 +1086,21 @@ static int plan_alloc(mg_sim *s, int M) {
     HIPC(hipDeviceSynchronize());
     (void)hipFree(s->plan_pool);
     s->plan_pool = nullptr; s->plan_cap = 0; s->plan_scores = nullptr; s->plan_rows = nullptr;
+    s->cem_thr = nullptr; s->cem_kthr = nullptr;
     MGState F = s->S;
     F.target_out = nullptr;   // nothing of a rollout reaches the bound outputs
     F.N = (M + 63) / 64 * 64;
     const size_t nrows = s->look_rows_host.size();
+    double *thr = nullptr;     // mg_plan_cem's elite threshold, per env
+    int32_t *kthr = nullptr;
     auto carve = [&](char *base, std::vector<StateRow> *rows, double **scores, PlanRow **table) {
         Carver c = {base, 0};
         c.rows = rows;
         layout(F, c, false);
         *scores = c.take<double>((size_t)F.N);
         *table = c.take<PlanRow>(nrows);
+        thr = c.take<double>((size_t)s->S.n_envs);
+        kthr = c.take<int32_t>((size_t)s->S.n_envs);
         return c.off + 256;
     };
     double *scores = nullptr;
@@ -1128,6 +1138,7 @@ static int plan_alloc(mg_sim *s, int M) {
     }
     s->FP = F;
     s->plan_pool = pool; s->plan_cap = M; s->plan_scores = scores; s->plan_rows = table;
+    s->cem_thr = thr; s->cem_kthr = kthr;
     return 0;
 }
 
@@ -1159,6 +1170,48 @@ int mg_plan_sample(mg_sim *s, uint8_t *actions, int32_t H, int32_t K, int32_t re
     if (H == 0) return 0;
     HIPC(hipSetDevice(s->device));
     HIPC(mg_launch_plan_sample(actions, s->S.n_envs, H, K, repeat, key, step, as_stream(stream)));
+    return 0;
+}
+
+int mg_plan_cem(mg_sim *s, uint8_t *actions, uint16_t *weights, int32_t warm, int32_t H, int32_t K, int32_t iters,
+                int32_t elites, int32_t alpha, int32_t repeat, uint64_t key, uint64_t step, const mg_plan_cem_out *out,
+                void *stream) {
+    if (!s || !actions || !weights || !out || !out->best)
+        return set_err(-22, "mg_plan_cem: null sim, actions_dev, weights_dev, out or out->best");
+    if (H < 1 || H > 4096) return set_err(-22, "mg_plan_cem: H must be in [1, 4096]");
+    if (int rc = plan_check_sizes(s, "mg_plan_cem", H, K)) return rc;
+    if (iters < 1 || iters > 64) return set_err(-22, "mg_plan_cem: iters must be in [1, 64]");
+    if (elites < 1 || elites > K) return set_err(-22, "mg_plan_cem: elites must be in [1, K]");
+    if (alpha < 0 || alpha > 1024) return set_err(-22, "mg_plan_cem: alpha must be in [0, 1024]");
+    if (repeat < 1) return set_err(-22, "mg_plan_cem: repeat must be at least 1");
+    if (warm != 0 && warm != 1) return set_err(-22, "mg_plan_cem: warm must be 0 or 1");
+    HIPC(hipSetDevice(s->device));
+    const int n = s->S.n_envs, M = K * n, J = (H + repeat - 1) / repeat;
+    if (M > s->plan_cap)
+        if (int rc = plan_alloc(s, M)) return rc;
+    hipStream_t st = as_stream(stream);
+    MGState F = s->FP;
+    F.n_envs = M;
+    double *scores = out->scores ? out->scores : s->plan_scores;
+    const LookOut lo = {scores, out->steps, nullptr, nullptr, out->errors};
+    CemUpdate u = {actions, weights, scores, s->cem_thr, s->cem_kthr, out->best, n, H, K, J, repeat, alpha,
+                   /*refit*/ 0, /*uniform*/ warm ? 0 : 1, /*draw*/ 1, /*incumbent*/ 0, key, step};
+    HIPC(mg_launch_cem_update(u, st));   // iteration 0's candidates
+    u.refit = 1; u.uniform = 0; u.incumbent = 1;
+    for (int i = 0; i < iters; i++) {
+        const bool last = i == iters - 1;
+        HIPC(mg_launch_plan_fan((const char *)s->pool, (char *)s->plan_pool, s->plan_rows, (int)s->look_rows_host.size(), n, K, st));
+        HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+        double *bs = out->iter_best ? out->iter_best + (size_t)i * n : last ? out->best_score : nullptr;
+        HIPC(mg_launch_plan_reduce(scores, actions, H, n, K, out->best, bs, out->first_action, st));
+        if (last && out->iter_best && out->best_score)
+            HIPC(hipMemcpyAsync(out->best_score, bs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPC(mg_launch_cem_threshold(scores, n, K, elites, s->cem_thr, s->cem_kthr, st));
+        // refit to this iteration's elites; unless it is the last, draw the next one's candidates over them
+        u.draw = last ? 0 : 1;
+        u.counter = step + (uint64_t)(i + 1) * (uint64_t)K * (uint64_t)J;
+        HIPC(mg_launch_cem_update(u, st));
+    }
     return 0;
 }
 

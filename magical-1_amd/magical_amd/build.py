@@ -21,8 +21,9 @@ _PHYS = _COMMON + ["mg_phys.h", "mg_step.h"]
 _STEP = _PHYS + ["mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h"]
 _LOOK = _STEP + ["mg_lookahead.h"]   # mg_lookahead's kernels: the step kernel's pairs with the env-step loop inside
 UNITS = {  # translation unit -> headers it depends on (one unit per kernel family: they compile in parallel)
-    "mg_sim.hip": _COMMON + ["mg_phys.h", "mg_snapshot.h", "mg_philox.h", "mg_plan.h"],
+    "mg_sim.hip": _COMMON + ["mg_phys.h", "mg_snapshot.h", "mg_philox.h", "mg_plan.h", "mg_cem.h"],
     "mg_plan.hip": ["mg_plan.h", "mg_philox.h"],   # mg_plan's fan-out copy, reduction and sampler (rollouts: mg_look_*)
+    "mg_cem.hip": ["mg_cem.h", "mg_philox.h"],     # mg_plan_cem's elite threshold and refit / draw kernels
     "mg_snapshot.hip": ["mg_common.h", "mg_snapshot.h"],
     "mg_physics.hip": _COMMON,
     "mg_reset.hip": _COMMON + ["mg_phys.h", "mg_reset.h"],

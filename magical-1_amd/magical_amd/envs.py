@@ -459,6 +459,51 @@ class VecMagicalEnv:
                                              int(step), self._stream()))
         return out
 
+    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False):
+        """Cross-entropy planning on the device (mg_plan_cem): `iters` rounds of K candidate sequences of H env-steps
+        per env (each action held for `repeat` steps, J = ceil(H / repeat) slots), every round rolled out as plan()
+        does, the per-env, per-slot action weights refitted to its `elites` best candidates (alpha + elite counts)
+        and, from the second round on, candidate 0 the best sequence so far.  Round i draws at counters step +
+        (i * K + k) * J + slot: a call consumes iters * K * J of them.  weights=None starts uniform; a contiguous
+        uint16 [J, 18, N] tensor on the env's device is the warm start and is updated in place.  Returns fresh device
+        tensors: 'best' i32[N] (index into the last round's candidates), 'best_score' f64[N], 'first_action' u8[N],
+        'plan' u8[H, N] (the best sequence), 'weights' u16[J, 18, N] (the given tensor when one was given),
+        'iter_best' f64[iters, N]; with details=True also 'actions' u8[H, K, N] (the last round's candidates) and
+        their 'scores' f64[K, N], 'steps' i32[K, N], 'errors' i32[K, N].  The envs are untouched, as by plan()."""
+        H, K, iters, repeat, n, dev = int(H), int(K), int(iters), int(repeat), self.num_envs, self.device
+        if H < 1 or K < 1 or iters < 1 or repeat < 1:
+            raise ValueError("plan_cem: H, K, iters and repeat must be at least 1")
+        if K * n > native.PLAN_MAX_ROLLOUTS:
+            raise ValueError(f"plan_cem: K * num_envs = {K * n} rollouts, more than {native.PLAN_MAX_ROLLOUTS}")
+        J = -(-H // repeat)
+        warm = weights is not None
+        if not warm:
+            weights = torch.empty((J, 18, n), dtype=torch.uint16, device=dev)
+        elif (not torch.is_tensor(weights) or tuple(weights.shape) != (J, 18, n) or weights.dtype != torch.uint16
+                or weights.device != dev or not weights.is_contiguous()):
+            raise ValueError(f"plan_cem: weights must be a contiguous uint16 [{J}, 18, {n}] tensor on {dev}")
+        acts = torch.empty((H, K, n), dtype=torch.uint8, device=dev)
+        res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
+                                       ("best_score", torch.empty(n, dtype=torch.float64, device=dev)),
+                                       ("first_action", torch.empty(n, dtype=torch.uint8, device=dev)),
+                                       ("iter_best", torch.empty((iters, n), dtype=torch.float64, device=dev))])
+        if details:
+            res["scores"] = torch.empty((K, n), dtype=torch.float64, device=dev)
+            res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+            res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+        out = native.mg_plan_cem_out(**{k: v.data_ptr() for k, v in res.items()})
+        native.check(self.lib.mg_plan_cem(self.handle, ctypes.c_void_p(acts.data_ptr()), ctypes.c_void_p(weights.data_ptr()),
+                                          int(warm), H, K, iters, int(elites), int(alpha), repeat, int(key), int(step),
+                                          ctypes.byref(out), self._stream()))
+        plan = acts.gather(1, res["best"].long()[None, None, :].expand(H, 1, n))[:, 0]
+        ordered = collections.OrderedDict([(k, res[k]) for k in ("best", "best_score", "first_action")])
+        ordered["plan"], ordered["weights"], ordered["iter_best"] = plan, weights, res["iter_best"]
+        if details:
+            ordered["actions"] = acts
+            for k in ("scores", "steps", "errors"):
+                ordered[k] = res[k]
+        return ordered
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.mg_destroy(self.handle)
@@ -554,6 +599,15 @@ class MagicalEnv:
             raise ValueError(f"plan: actions must be [H, K], got {tuple(a.shape)}")
         res = self._vec.plan(a[:, :, None], details=True)
         return int(res["best"][0].item()), float(res["best_score"][0].item()), res["scores"][:, 0].cpu().numpy()
+
+    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0):
+        """Cross-entropy planning from the current state, which stays as it is (VecMagicalEnv.plan_cem for this one
+        env, from uniform weights).  Returns (plan, best_score, iter_best): the best action sequence found as a
+        uint8 array [H], its score, and the best score of every iteration as a float64 array [iters]."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before plan_cem()")
+        res = self._vec.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key, step=step)
+        return res["plan"][:, 0].cpu().numpy(), float(res["best_score"][0].item()), res["iter_best"][:, 0].cpu().numpy()
 
     def get_state(self):
         """The env's whole state as bytes (a one-record snapshot blob, magical_amd.snapshot): physics, RNG, episode

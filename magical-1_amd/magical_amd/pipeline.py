@@ -272,6 +272,39 @@ class PipelinedVecEnv:
             out[:, :, b[k]:b[k + 1]] = sim.sample_plans(H, K, repeat=repeat, key=key + k, step=step)
         return out
 
+    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False):
+        """VecMagicalEnv.plan_cem for the whole pool: chunk k plans its envs [bounds[k], bounds[k + 1]) on its own
+        stream with key + k (envs numbered from 0, as sample_plans), and the results are concatenated in env order.
+        weights: None, or a uint16 [J, 18, num_envs] tensor on the pool's device, the warm start, updated in place
+        (each chunk works on its own contiguous copy of its columns, which is copied back)."""
+        J = -(-int(H) // max(int(repeat), 1))
+        if weights is not None and (not torch.is_tensor(weights) or tuple(weights.shape) != (J, 18, self.num_envs)
+                                    or weights.dtype != torch.uint16 or weights.device != self.device):
+            raise ValueError(f"plan_cem: weights must be a uint16 [{J}, 18, {self.num_envs}] tensor on {self.device}")
+        self.wait()
+        self._fork()
+        b, parts = self.bounds, []
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            with torch.cuda.stream(st):
+                w = (None if weights is None
+                     else weights.view(torch.int16)[:, :, b[k]:b[k + 1]].contiguous().view(torch.uint16))
+                parts.append(sim.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key + k, step=step,
+                                          weights=w, details=details))
+        self.wait()
+        out = collections.OrderedDict()
+        for name in parts[0]:
+            ts = [p[name] for p in parts]
+            if ts[0].dtype == torch.uint16:   # (moved as int16: the same bytes, a type every torch op takes)
+                out[name] = torch.cat([t.view(torch.int16) for t in ts], dim=-1).view(torch.uint16)
+            else:
+                out[name] = torch.cat(ts, dim=-1)   # envs are the last axis of every result
+            for p in parts:   # allocated on the chunks' streams, read here on the caller's
+                p[name].record_stream(self._caller())
+        if weights is not None:
+            weights.view(torch.int16).copy_(out["weights"].view(torch.int16))
+            out["weights"] = weights
+        return out
+
     def _obs(self):
         from .envs import window_stack
         allo, ego, past = self.buffers.get("allo"), self.buffers.get("ego"), self.buffers.get("past_obs")
