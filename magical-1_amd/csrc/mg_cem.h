@@ -1,7 +1,7 @@
 // mg_cem.h -- mg_plan_cem's own kernels (mg_cem.hip): the elite threshold of an iteration's scores and the per-slot
 // update (refit of the sampling weights to the elites, draw of the next iteration's candidates).  The rollouts, the
-// fan-out and the best-of-K reduction are mg_plan's, launched unchanged (mg_plan.h, mg_lookahead.h); the C ABI and the
-// iteration loop live in mg_sim.hip.
+// fan-out and the best-of-K reduction are mg_plan's, launched unchanged (mg_plan.h, mg_lookahead.h); mg_plan_cem and its
+// iteration loop are in mg_cem.hip as well.
 //
 // Layouts (n = num_envs, J = ceil(H / repeat) held-action slots): candidates u8[H][K][n] as mg_plan takes them,
 // scores f64[K][n], weights u16[J][18][n] -- slot j, action a, env e at (j * 18 + a) * n + e -- so everything that

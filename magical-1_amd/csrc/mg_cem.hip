@@ -1,5 +1,6 @@
-// mg_cem.hip -- mg_plan_cem's elite threshold and per-slot update kernels (mg_cem.h; the rollouts, the fan-out and the
-// reduction are mg_plan's, the C ABI and the iteration loop live in mg_sim.hip).
+// mg_cem.hip -- mg_plan_cem, its iteration loop, and its elite threshold and per-slot update kernels (mg_cem.h; the
+// rollouts, the fan-out, the reduction and the fan pool are mg_plan's).
+#include "mg_sim.h"
 #include "mg_cem.h"
 #include "mg_philox.h"
 
@@ -128,4 +129,46 @@ hipError_t mg_launch_cem_update(const CemUpdate &u, hipStream_t st) {
     const uint64_t total = (uint64_t)u.J * u.n_envs;   // <= 4096 * num_envs <= 2^30
     hipLaunchKernelGGL(cem_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u);
     return hipGetLastError();
+}
+
+extern "C" int mg_plan_cem(mg_sim *s, uint8_t *actions, uint16_t *weights, int32_t warm, int32_t H, int32_t K,
+                           int32_t iters, int32_t elites, int32_t alpha, int32_t repeat, uint64_t key, uint64_t step,
+                           const mg_plan_cem_out *out, void *stream) {
+    if (!s || !actions || !weights || !out || !out->best)
+        return set_err(-22, "mg_plan_cem: null sim, actions_dev, weights_dev, out or out->best");
+    if (H < 1 || H > 4096) return set_err(-22, "mg_plan_cem: H must be in [1, 4096]");
+    if (int rc = plan_check_sizes(s, "mg_plan_cem", H, K)) return rc;
+    if (iters < 1 || iters > 64) return set_err(-22, "mg_plan_cem: iters must be in [1, 64]");
+    if (elites < 1 || elites > K) return set_err(-22, "mg_plan_cem: elites must be in [1, K]");
+    if (alpha < 0 || alpha > 1024) return set_err(-22, "mg_plan_cem: alpha must be in [0, 1024]");
+    if (repeat < 1) return set_err(-22, "mg_plan_cem: repeat must be at least 1");
+    if (warm != 0 && warm != 1) return set_err(-22, "mg_plan_cem: warm must be 0 or 1");
+    HIPC(hipSetDevice(s->device));
+    const int n = s->main.S.n_envs, M = K * n, J = (H + repeat - 1) / repeat;
+    RolloutPool &R = s->fan;
+    if (int rc = rollout_reserve(s, R, M, "mg_plan_cem")) return rc;
+    hipStream_t st = as_stream(stream);
+    MGState F = R.P.S;
+    F.n_envs = M;
+    double *scores = out->scores ? out->scores : R.scores;
+    const LookOut lo = {scores, out->steps, nullptr, nullptr, out->errors};
+    CemUpdate u = {actions, weights, scores, R.cem_thr, R.cem_kthr, out->best, n, H, K, J, repeat, alpha,
+                   /*refit*/ 0, /*uniform*/ warm ? 0 : 1, /*draw*/ 1, /*incumbent*/ 0, key, step};
+    HIPC(mg_launch_cem_update(u, st));   // iteration 0's candidates
+    u.refit = 1; u.uniform = 0; u.incumbent = 1;
+    for (int i = 0; i < iters; i++) {
+        const bool last = i == iters - 1;
+        HIPC(mg_launch_plan_fan((const char *)s->main.mem, (char *)R.P.mem, R.rows, R.nrows, n, K, st));
+        HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+        double *bs = out->iter_best ? out->iter_best + (size_t)i * n : last ? out->best_score : nullptr;
+        HIPC(mg_launch_plan_reduce(scores, actions, H, n, K, out->best, bs, out->first_action, st));
+        if (last && out->iter_best && out->best_score)
+            HIPC(hipMemcpyAsync(out->best_score, bs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPC(mg_launch_cem_threshold(scores, n, K, elites, R.cem_thr, R.cem_kthr, st));
+        // refit to this iteration's elites; unless it is the last, draw the next one's candidates over them
+        u.draw = last ? 0 : 1;
+        u.counter = step + (uint64_t)(i + 1) * (uint64_t)K * (uint64_t)J;
+        HIPC(mg_launch_cem_update(u, st));
+    }
+    return 0;
 }

@@ -1,6 +1,6 @@
 // mg_launch.h -- host-side launchers of the device kernels (one translation unit per kernel family: mg_reset.hip,
-// mg_step_*.hip with their dispatch in mg_physics.hip, mg_raster.hip; the C ABI lives in mg_sim.hip).  The step
-// kernel's forms, slot caps and LDS view: mg_stepforms.h.
+// mg_step_*.hip with their dispatch in mg_physics.hip, mg_raster.hip).  The C ABI calls them from the unit that holds the
+// feature (mg_sim.h lists which).  The step kernel's forms, slot caps and LDS view: mg_stepforms.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mg_state.h"

@@ -1,17 +1,32 @@
-// mg_plan.h -- mg_plan's own kernels (mg_plan.hip): the fan-out copy of the sim's state into the fan pool, the
-// best-of-K reduction and the candidate sampler of mg_plan_sample.  The rollouts themselves are the lookahead kernel
-// (mg_lookahead.h), launched unchanged on the fan pool; the C ABI, the pool and its allocation live in mg_sim.hip.
+// mg_plan.h -- rollout pools and mg_plan's own kernels (mg_plan.hip, with mg_plan / mg_plan_sample and the pools'
+// allocation): the fan-out copy of the sim's state into a rollout pool, the best-of-K reduction and the candidate
+// sampler of mg_plan_sample.  The rollouts themselves are the lookahead kernel (mg_lookahead.h), launched unchanged on
+// the pool.
 //
-// The fan pool is an MGState of M = K * num_envs envs, laid out as the lookahead scratch is (every [slot][Mpad] row,
-// no frame rings).  Rollout r = k * num_envs + e -- candidate k of env e -- is its env r, so one candidate's envs are
+// A rollout pool is a StatePool of M = K * num_envs envs (every [slot][Mpad] row, no frame rings); mg_lookahead's is
+// the case K = 1.  Rollout r = k * num_envs + e -- candidate k of env e -- is its env r, so one candidate's envs are
 // contiguous in every row and everything that runs along e is coalesced: the copy's stores, the action bytes
 // (u8[H][K][num_envs] is u8[H][M]), the [K][num_envs] outputs and the reduction's reads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mg_pool.h"
 
 // one state row of the fan-out: env e's element at src_pool + src + e * esize, rollout r's at dst_pool + dst + r * esize
 struct PlanRow { uint64_t src, dst; uint32_t esize, pad; };
+
+// One allocation (P.mem) holds the state rows, the rollouts' scores (f64[P.S.N]: the reduction's input also when the
+// caller wants no scores), the device table of the fan-out's rows (the rollout rows of the sim's pool zipped with this
+// pool's) and mg_plan_cem's per-env scratch, the elite threshold (cem_thr f64[num_envs], cem_kthr i32[num_envs])
+struct RolloutPool {
+    StatePool P;
+    PlanRow *rows = nullptr;
+    int nrows = 0;
+    int cap = 0;   // rollouts
+    double *scores = nullptr;
+    double *cem_thr = nullptr;
+    int32_t *cem_kthr = nullptr;
+};
 
 // dst column k * n_envs + e <- src column e, for every row, k < K and e < n_envs
 hipError_t mg_launch_plan_fan(const char *src_pool, char *dst_pool, const PlanRow *rows_dev, int nrows, int n_envs, int K,

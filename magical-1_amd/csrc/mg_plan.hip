@@ -1,6 +1,8 @@
-// mg_plan.hip -- mg_plan's fan-out copy, best-of-K reduction and candidate sampler (mg_plan.h; the rollouts are the
-// lookahead kernel on the fan pool, the C ABI and the pool live in mg_sim.hip).
-#include "mg_plan.h"
+// mg_plan.hip -- mg_plan / mg_plan_sample, the rollout pools' allocation, and mg_plan's fan-out copy, best-of-K
+// reduction and candidate sampler (mg_plan.h; the rollouts are the lookahead kernel on the fan pool).
+#include <cassert>
+
+#include "mg_sim.h"
 #include "mg_philox.h"
 
 // Fan-out: a workgroup takes PLAN_ROWS_PER_WG rows of its 256 envs, reads each source element once into registers
@@ -10,10 +12,24 @@
 // word is always aligned (rows start on 4-byte boundaries and are padded to 64 envs), the destination word of candidate
 // k is when k * n_envs elements are a whole number of words -- every k when n_envs is a multiple of 4 -- and otherwise,
 // or where the word would run past the candidate's last env, the lane stores its elements one by one.
+//
+// ONE (K = 1, mg_lookahead's copy): nothing is stored twice, so a lane moves its own env's element of each row and
+// nothing is packed -- the fan path with one candidate measured 0.035 ms (MoveToRegion, 4096 envs) and 0.06 ms
+// (ClusterColour, 8192 envs) slower per lookahead than this plain copy.
 #define PLAN_ROWS_PER_WG 8
+template <bool ONE>
 __global__ void __launch_bounds__(256) plan_fan_kernel(const char *__restrict__ src, char *__restrict__ dst,
                                                        const PlanRow *__restrict__ rows, int nrows, int n_envs, int K) {
     const int tid = threadIdx.x, r0 = blockIdx.y * PLAN_ROWS_PER_WG;
+    if (ONE) {
+        const int e = blockIdx.x * 256 + tid;
+        if (e >= n_envs) return;
+        for (int r = r0; r < r0 + PLAN_ROWS_PER_WG && r < nrows; r++) {
+            const PlanRow w = rows[r];   // uniform over the workgroup
+            copy_elem(dst + w.dst + (size_t)e * w.esize, src + w.src + (size_t)e * w.esize, w.esize);
+        }
+        return;
+    }
     PlanRow w[PLAN_ROWS_PER_WG];   // uniform over the workgroup
     uint64_t v[PLAN_ROWS_PER_WG];
     int e0[PLAN_ROWS_PER_WG];      // the lane's first env of the row; -1: none
@@ -58,8 +74,9 @@ __global__ void __launch_bounds__(256) plan_fan_kernel(const char *__restrict__ 
 
 hipError_t mg_launch_plan_fan(const char *src_pool, char *dst_pool, const PlanRow *rows_dev, int nrows, int n_envs, int K,
                               hipStream_t st) {
-    hipLaunchKernelGGL(plan_fan_kernel, dim3((n_envs + 255) / 256, (nrows + PLAN_ROWS_PER_WG - 1) / PLAN_ROWS_PER_WG),
-                       dim3(256), 0, st, src_pool, dst_pool, rows_dev, nrows, n_envs, K);
+    hipLaunchKernelGGL(K == 1 ? plan_fan_kernel<true> : plan_fan_kernel<false>,
+                       dim3((n_envs + 255) / 256, (nrows + PLAN_ROWS_PER_WG - 1) / PLAN_ROWS_PER_WG), dim3(256), 0, st,
+                       src_pool, dst_pool, rows_dev, nrows, n_envs, K);
     return hipGetLastError();
 }
 
@@ -108,3 +125,83 @@ hipError_t mg_launch_plan_sample(uint8_t *out, int n_envs, int H, int K, int rep
                        repeat, key, step);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// C ABI
+int plan_check_sizes(const mg_sim *s, const char *fn, int32_t H, int32_t K) {
+    if (H < 0 || H > 4096) return set_err(-22, std::string(fn) + ": H must be in [0, 4096]");
+    if (K < 1 || K > 4096) return set_err(-22, std::string(fn) + ": K must be in [1, 4096]");
+    if ((int64_t)K * s->main.S.n_envs > MG_PLAN_MAX_ROLLOUTS)
+        return set_err(-22, std::string(fn) + ": K * num_envs = " + std::to_string((int64_t)K * s->main.S.n_envs) +
+                                " rollouts, more than MG_PLAN_MAX_ROLLOUTS = " + std::to_string(MG_PLAN_MAX_ROLLOUTS));
+    return 0;
+}
+
+// (Re)allocate R for M rollouts unless it holds as many.  The device is synchronised first: an earlier call's kernels
+// may still be running on the pool that is freed here.  On failure the sim is without this pool and stays usable (the
+// next call allocates again)
+int rollout_reserve(mg_sim *s, RolloutPool &R, int M, const char *fn) {
+    if (M <= R.cap) return 0;
+    HIPC(hipDeviceSynchronize());
+    pool_free(R.P);
+    R = RolloutPool();
+    const std::vector<StateRow> src = pool_rollout_rows(s->main);
+    RolloutPool T;
+    hipError_t err = pool_create(T.P, s->main.S, (M + 63) / 64 * 64, false, [&](Carver &c) {
+        T.scores = c.take<double>((size_t)T.P.S.N);
+        T.rows = c.take<PlanRow>(src.size());
+        T.cem_thr = c.take<double>((size_t)s->main.S.n_envs);
+        T.cem_kthr = c.take<int32_t>((size_t)s->main.S.n_envs);
+    });
+    if (err != hipSuccess)
+        return set_err(-12, std::string(fn) + ": rollout pool for " + std::to_string(M) + " rollouts: " + hipGetErrorString(err));
+    // layout() lists every pool's rows in the same order: row i of both lists is the same field
+    const std::vector<StateRow> dst = pool_rollout_rows(T.P);
+    assert(dst.size() == src.size());
+    std::vector<PlanRow> pr;
+    for (size_t i = 0; i < src.size(); i++) pr.push_back(PlanRow{src[i].off, dst[i].off, src[i].esize, 0u});
+    err = hipMemcpy(T.rows, pr.data(), pr.size() * sizeof(PlanRow), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        pool_free(T.P);
+        return set_err(-12, std::string(fn) + ": rollout pool setup: " + hipGetErrorString(err));
+    }
+    T.nrows = (int)pr.size();
+    T.cap = M;
+    R = T;
+    return 0;
+}
+
+extern "C" {
+
+int mg_plan(mg_sim *s, const uint8_t *actions, int32_t H, int32_t K, const mg_plan_out *out, void *stream) {
+    if (!s || !out || !out->best) return set_err(-22, "mg_plan: null sim, out or out->best");
+    if (int rc = plan_check_sizes(s, "mg_plan", H, K)) return rc;
+    if (!actions && H > 0) return set_err(-22, "mg_plan: null actions with H > 0");
+    HIPC(hipSetDevice(s->device));
+    const int n = s->main.S.n_envs, M = K * n;
+    RolloutPool &R = s->fan;
+    if (int rc = rollout_reserve(s, R, M, "mg_plan")) return rc;
+    hipStream_t st = as_stream(stream);
+    // the pool may be larger than this call needs: its rows keep the stride it was laid out with, the launch covers M
+    MGState F = R.P.S;
+    F.n_envs = M;
+    HIPC(mg_launch_plan_fan((const char *)s->main.mem, (char *)R.P.mem, R.rows, R.nrows, n, K, st));
+    double *scores = out->scores ? out->scores : R.scores;
+    const LookOut lo = {scores, out->steps, nullptr, nullptr, out->errors};
+    HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+    HIPC(mg_launch_plan_reduce(scores, actions, H, n, K, out->best, out->best_score, out->first_action, st));
+    return 0;
+}
+
+int mg_plan_sample(mg_sim *s, uint8_t *actions, int32_t H, int32_t K, int32_t repeat, uint64_t key, uint64_t step,
+                   void *stream) {
+    if (!s || !actions) return set_err(-22, "mg_plan_sample: null argument");
+    if (repeat < 1) return set_err(-22, "mg_plan_sample: repeat must be at least 1");
+    if (int rc = plan_check_sizes(s, "mg_plan_sample", H, K)) return rc;
+    if (H == 0) return 0;
+    HIPC(hipSetDevice(s->device));
+    HIPC(mg_launch_plan_sample(actions, s->main.S.n_envs, H, K, repeat, key, step, as_stream(stream)));
+    return 0;
+}
+
+} // extern "C"

@@ -11,7 +11,7 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "mg_common.h"
+#include "mg_sim.h"
 
 namespace {
 constexpr int RES = MG_RES, LO = MG_LORES;
@@ -276,7 +276,6 @@ extern "C" hipError_t mg_launch_restack_window(const uint8_t *recv, int32_t worl
     return hipGetLastError();
 }
 
-// launcher, C linkage (declared in mg_sim.hip next to the ABI entry mg_replay_lores)
 extern "C" hipError_t mg_launch_replay(const uint8_t *frames, int32_t nframes, const int32_t *episode_start,
                                        int32_t preproc, uint8_t *scratch, uint8_t *out_allo, uint8_t *out_ego,
                                        uint8_t *out_past, hipStream_t st) {
@@ -310,3 +309,75 @@ extern "C" hipError_t mg_launch_restack(const uint8_t *recv, int32_t world, int3
                        (uint32_t)(step & 3), all_fresh, ring, two ? out_allo : out_past, out_ego);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// C ABI: argument checks, then the launchers above
+extern "C" {
+
+int mg_replay_lores(const uint8_t *frames, int32_t nframes, const int32_t *episode_start, int32_t preproc,
+                    uint8_t *scratch, uint8_t *out_allo, uint8_t *out_ego, uint8_t *out_past, void *stream) {
+    if (nframes <= 0 || !frames || !episode_start || !scratch || !out_allo || !out_ego)
+        return set_err(-22, "mg_replay_lores: null argument or nframes <= 0");
+    if (preproc != MG_PREPROC_LORES4E && preproc != MG_PREPROC_LORESSTACK && preproc != MG_PREPROC_LORES3EA &&
+        preproc != MG_PREPROC_LORES4A)
+        return set_err(-22, "mg_replay_lores: preproc must be 1 (LoRes4E), 2 (LoResStack), 3 (LoRes3EA) or 4 (LoRes4A)");
+    if (preproc != MG_PREPROC_LORESSTACK && !out_past) return set_err(-22, "mg_replay_lores: out_past required");
+    const void *ptrs[6] = {frames, scratch, out_allo, out_ego, out_past ? out_past : out_allo, episode_start};
+    for (const void *p : ptrs)
+        if (((uintptr_t)p & 15) != 0) return set_err(-22, "mg_replay_lores: buffers must be 16-byte aligned");
+    HIPC(mg_launch_replay(frames, nframes, episode_start, preproc, scratch, out_allo, out_ego, out_past,
+                          as_stream(stream)));
+    return 0;
+}
+
+int mg_restack(const uint8_t *recv, int32_t world, int32_t n, int64_t rank_stride, int64_t off_allo, int64_t off_ego,
+               int64_t off_done, int32_t preproc, int64_t step, int32_t all_fresh, uint8_t *ring, uint8_t *out_allo,
+               uint8_t *out_ego, uint8_t *out_past, void *stream) {
+    if (!recv || !ring || world <= 0 || n <= 0 || step < 0) return set_err(-22, "mg_restack: null argument or bad size");
+    const int64_t FR = (int64_t)MG_LORES * MG_LORES * 3;
+    if ((int64_t)world * n * (MG_LORES * MG_LORES / 4) >= ((int64_t)1 << 31))
+        return set_err(-22, "mg_restack: world * n too large for one launch");
+    if (preproc == MG_PREPROC_LORESSTACK) {
+        if (!out_allo || !out_ego) return set_err(-22, "mg_restack: LoResStack needs out_allo and out_ego");
+    } else if (preproc == MG_PREPROC_LORES4E || preproc == MG_PREPROC_LORES4A || preproc == MG_PREPROC_LORES3EA) {
+        if (!out_past) return set_err(-22, "mg_restack: out_past required for this preprocessor");
+    } else {
+        return set_err(-22, "mg_restack: preproc must be 1 (LoRes4E), 2 (LoResStack), 3 (LoRes3EA) or 4 (LoRes4A)");
+    }
+    if (off_allo < 0 || off_ego < 0 || off_done < 0 || off_allo + n * FR > rank_stride || off_ego + n * FR > rank_stride ||
+        off_done + n > rank_stride)
+        return set_err(-22, "mg_restack: a key of the rank block lies outside rank_stride");
+    const int64_t al[4] = {(int64_t)(uintptr_t)recv, rank_stride, off_allo, off_ego};
+    for (int64_t a : al)
+        if (a & 15) return set_err(-22, "mg_restack: recv, rank_stride and frame offsets must be 16-byte aligned");
+    const void *ptrs[4] = {ring, out_allo, out_ego, out_past};
+    for (const void *p : ptrs)
+        if (((uintptr_t)p & 15) != 0) return set_err(-22, "mg_restack: buffers must be 16-byte aligned");
+    HIPC(mg_launch_restack(recv, world, n, rank_stride, off_allo, off_ego, off_done, preproc, step, all_fresh, ring,
+                           out_allo, out_ego, out_past, as_stream(stream)));
+    return 0;
+}
+
+int mg_restack_window(const uint8_t *recv, int32_t world, int32_t n, int64_t rank_stride, int64_t off_allo,
+                      int64_t off_ego, int64_t off_done, int32_t preproc, int64_t step, int32_t all_fresh, int32_t K,
+                      uint8_t *ring, void *stream) {
+    if (!recv || !ring || world <= 0 || n <= 0 || step < 0) return set_err(-22, "mg_restack_window: null argument or bad size");
+    if (K < 4 || K > 64) return set_err(-22, "mg_restack_window: K must be in [4, 64]");
+    if (preproc != MG_PREPROC_LORES4E && preproc != MG_PREPROC_LORESSTACK && preproc != MG_PREPROC_LORES4A)
+        return set_err(-22, "mg_restack_window: preproc must be 1 (LoRes4E), 2 (LoResStack) or 4 (LoRes4A); "
+                            "LoRes3EA's stack is not one ring's window (use mg_restack)");
+    if ((int64_t)world * n * (MG_LORES * MG_LORES / 16) >= ((int64_t)1 << 31))
+        return set_err(-22, "mg_restack_window: world * n too large for one launch");
+    const int64_t FR = (int64_t)MG_LORES * MG_LORES * 3;
+    if (off_allo < 0 || off_ego < 0 || off_done < 0 || off_allo + n * FR > rank_stride || off_ego + n * FR > rank_stride ||
+        off_done + n > rank_stride)
+        return set_err(-22, "mg_restack_window: a key of the rank block lies outside rank_stride");
+    const int64_t al[5] = {(int64_t)(uintptr_t)recv, rank_stride, off_allo, off_ego, (int64_t)(uintptr_t)ring};
+    for (int64_t a : al)
+        if (a & 15) return set_err(-22, "mg_restack_window: recv, ring, rank_stride and frame offsets must be 16-byte aligned");
+    HIPC(mg_launch_restack_window(recv, world, n, rank_stride, off_allo, off_ego, off_done, preproc, step, all_fresh, K,
+                                  ring, as_stream(stream)));
+    return 0;
+}
+
+} // extern "C"

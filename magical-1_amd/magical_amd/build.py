@@ -16,26 +16,28 @@ INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "magic
 OBJDIR = os.path.join(os.path.dirname(HERE), "build")
 OUT = os.path.join(HERE, "libmagical_sim.so")
 PROF_OUT = os.path.join(HERE, "libmagical_sim_prof.so")  # -DMG_PROFILE phase timers (tools/gpu_phase.py)
-_COMMON = ["mg_common.h", "mg_math.h", "mg_state.h", "mg_stepforms.h", "mg_launch.h", "mg_prof.h"]
-_PHYS = _COMMON + ["mg_phys.h", "mg_step.h"]
-_STEP = _PHYS + ["mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h"]
+_LAUNCH = ["mg_common.h", "mg_state.h", "mg_stepforms.h", "mg_launch.h"]
+_PHYS = _LAUNCH + ["mg_math.h", "mg_phys.h", "mg_prof.h"]
+_STEP = _PHYS + ["mg_step.h", "mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h"]
 _LOOK = _STEP + ["mg_lookahead.h"]   # mg_lookahead's kernels: the step kernel's pairs with the env-step loop inside
-UNITS = {  # translation unit -> headers it depends on (one unit per kernel family: they compile in parallel)
-    "mg_sim.hip": _COMMON + ["mg_phys.h", "mg_snapshot.h", "mg_philox.h", "mg_plan.h", "mg_cem.h"],
-    "mg_plan.hip": ["mg_plan.h", "mg_philox.h"],   # mg_plan's fan-out copy, reduction and sampler (rollouts: mg_look_*)
-    "mg_cem.hip": ["mg_cem.h", "mg_philox.h"],     # mg_plan_cem's elite threshold and refit / draw kernels
-    "mg_snapshot.hip": ["mg_common.h", "mg_snapshot.h"],
-    "mg_physics.hip": _COMMON,
-    "mg_reset.hip": _COMMON + ["mg_phys.h", "mg_reset.h"],
+_SIM = _LAUNCH + ["mg_sim.h", "mg_pool.h", "mg_plan.h", "mg_snapshot.h"]   # the units that hold a part of the C ABI
+UNITS = {  # translation unit -> every header it includes, directly or not (one unit per kernel family: they compile
+    # in parallel); tests/test_lookahead_host.py checks the lists against the #include lines
+    "mg_sim.hip": _SIM + ["mg_math.h", "mg_phys.h", "mg_philox.h"],
+    "mg_plan.hip": _SIM + ["mg_philox.h"],   # mg_plan, rollout pools, fan-out copy, reduction, sampler (rollouts: mg_look_*)
+    "mg_cem.hip": _SIM + ["mg_cem.h", "mg_philox.h"],   # mg_plan_cem, its elite threshold and refit / draw kernels
+    "mg_snapshot.hip": _SIM,
+    "mg_physics.hip": _LAUNCH,
+    "mg_reset.hip": _PHYS + ["mg_reset.h"],
     "mg_step_v4.hip": _STEP,
     "mg_step_quad.hip": _STEP,
     "mg_step_hbm.hip": _STEP,
-    "mg_lookahead.hip": _COMMON,
+    "mg_lookahead.hip": _SIM,
     "mg_look_v4.hip": _LOOK,
     "mg_look_quad.hip": _LOOK,
     "mg_look_hbm.hip": _LOOK,
-    "mg_raster.hip": _PHYS + ["mg_render.h"],
-    "mg_replay.hip": ["mg_common.h"],
+    "mg_raster.hip": _PHYS + ["mg_step.h", "mg_render.h"],
+    "mg_replay.hip": _SIM,
 }
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 

@@ -93,6 +93,39 @@ def test_bit_identical_to_stepping(name, env, n, pair, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 3, 65, 70])
+@pytest.mark.parametrize("name", [REGION, CLUSTER])
+def test_ragged_env_counts_and_separate_pools(name, n):
+    """The scratch copy is mg_plan's fan-out with one candidate.  Env counts that are no multiple of 4 (the last lane's
+    packed 1- and 2-byte words would run past the last env) or of 64: a lookahead of 3 actions = a twin stepped through
+    them, the sim's state dumps before = after.  Then lookahead, plan (2 candidates, its own pool), lookahead on the
+    same sim: what a sim that only ever looked ahead returns, and the next step of both is the same."""
+    H, W0 = 3, 6
+    acts = script(W0 + H + 1, n)
+    a, b, c = (warm(make(name, n, **kw), acts, W0) for kw in ({}, {"auto_reset": False}, {}))
+    before = (a.bodies(), a.errors(), a.arbiters())
+    la = a.lookahead(acts[W0:W0 + H], bodies=True)
+    after = (a.bodies(), a.errors(), a.arbiters())
+    assert torch.equal(before[0][0], after[0][0]) and torch.equal(before[0][1], after[0][1])
+    assert torch.equal(before[1], after[1])
+    assert torch.equal(before[2][0], after[2][0]) and torch.equal(before[2][1].view(torch.int64), after[2][1].view(torch.int64))
+    for t in range(H):
+        b.step(acts[W0 + t])
+    bodies, counts = b.bodies()
+    assert torch.equal(la["bodies"], bodies) and torch.equal(la["counts"], counts)
+    assert torch.equal(la["steps"], torch.full((n,), H, dtype=torch.int32, device="cuda"))
+    assert torch.equal(la["errors"], b.errors())
+    cands = torch.stack([acts[W0:W0 + H], acts[W0 + 1:W0 + H + 1]], dim=1)   # [H, 2, n]
+    plan = a.plan(cands, details=True)
+    assert torch.equal(plan["scores"][0], la["score"])   # candidate 0 is the lookahead's sequence
+    again = a.lookahead(acts[W0:W0 + H], bodies=True)
+    only = [c.lookahead(acts[W0:W0 + H], bodies=True) for _ in range(2)]
+    same(la, only[0], "first"), same(again, only[1], "after a plan")
+    same(step_out(a, acts[W0 + H]), step_out(c, acts[W0 + H]), "next step")
+    a.close(), b.close(), c.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name,L", [(REGION, FAR), (CORNER, FAR), ("MatchRegions-TestAll-LoResStack-v0", 9),
                                     ("PickAndPlace-Demo-LoRes4E-v0", 9)])
 def test_sim_is_untouched(name, L):

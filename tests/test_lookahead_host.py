@@ -36,6 +36,19 @@ def test_binding_matches_the_header():
     assert fn(None, None, 1, None, None) == -22
 
 
+def test_build_table_matches_the_include_lines():
+    """a header missing from a unit's list is a stale-object bug: every list is exactly what the unit includes, directly
+    or through its headers"""
+    def includes(f, seen):
+        for h in re.findall(r'^#include "(mg_\w+\.h)"', open(os.path.join(build.CSRC, f)).read(), re.M):
+            if h not in seen:
+                seen.add(h)
+                includes(h, seen)
+        return seen
+    for u, hs in build.UNITS.items():
+        assert sorted(hs) == sorted(includes(u, set())), u
+
+
 def test_build_lists_the_lookahead_units():
     units = [u for u in build.UNITS if "look" in u]
     assert sorted(units) == ["mg_look_hbm.hip", "mg_look_quad.hip", "mg_look_v4.hip", "mg_lookahead.hip"]

@@ -6,6 +6,8 @@ max_episode_steps = 9 with episode phases staggered 0..8, so some envs auto-rese
 and every env does within 9; actions from random_actions(step).
 """
 import ctypes
+import json
+import os
 
 import numpy as np
 import pytest
@@ -340,3 +342,32 @@ def test_restored_continuation_matches_oracle():
     for i in range(n):
         assert np.array_equal(flat[i], ref[i]), i
     vec.close()
+
+
+@pytest.mark.gpu
+def test_blob_format_is_stable():
+    """tests/golden/snapshot_blob.bin was written by the library that introduced blob layout version 1 (3 envs of
+    MoveToRegion-Demo-v0 -- no preprocessor: state sections only -- 5 steps, envs [2, 0]; make_snapshot_blob.py).  The
+    same run writes the same bytes today, and the file restores into a fresh sim that then steps as the recorded one."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(golden, "snapshot_blob.json")) as f:
+        meta = json.load(f)
+    want = torch.from_numpy(np.fromfile(os.path.join(golden, "snapshot_blob.bin"), dtype=np.uint8))
+    acts = torch.as_tensor(meta["actions"], dtype=torch.uint8)
+    envs, t0 = meta["envs"], meta["before"]
+    a = mg_envs.VecMagicalEnv(meta["name"], len(meta["seeds"]), seeds=meta["seeds"])
+    b = mg_envs.VecMagicalEnv(meta["name"], len(meta["seeds"]), seeds=meta["seeds"])
+    a.reset(), b.reset()
+    for t in range(t0):
+        a.step(acts[t])
+    # mg_snapshot does not write the padding that rounds a record's state bytes up to 16: the buffer is zeroed first, as
+    # the fixture's was
+    got = a.snapshot(envs=envs, out=torch.zeros(want.numel(), dtype=torch.uint8, device="cuda")).blob.cpu()
+    assert got.numel() == want.numel()
+    assert torch.equal(got, want), ("first differing byte", int((got != want).nonzero()[0]))
+    b.restore(Snapshot(want), envs=envs)
+    for t in range(t0, t0 + meta["after"]):
+        a.step(acts[t]), b.step(acts[t])
+        (ba, ca), (bb, cb) = a.bodies(), b.bodies()
+        assert torch.equal(ba[envs], bb[envs]) and torch.equal(ca[envs], cb[envs]), t
+    a.close(), b.close()

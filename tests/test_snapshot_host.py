@@ -39,6 +39,18 @@ def test_snapshot_bytes_is_linear_above_the_header(name):
     assert snapshot_bytes(name, -1) < 0
 
 
+# mg_snapshot_bytes(name, 1) and (name, 70) of the library that wrote blob layout version 1: the row count and the state
+# section's bytes are part of the format, wherever layout() lives
+PINNED = {"MoveToRegion-Demo-LoRes4E-v0": (190304, 13303616), "ClusterColour-Demo-LoResStack-v0": (245600, 17174336),
+          "MoveToCorner-Demo-LoRes3EA-v0": (190304, 13303616), "MoveToRegion-Demo-LoRes4A-v0": (162656, 11368256),
+          "MoveToRegion-Demo-v0": (24416, 1691456)}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_snapshot_bytes_is_pinned(name):
+    assert (snapshot_bytes(name, 1), snapshot_bytes(name, 70)) == PINNED[name]
+
+
 def test_record_size_depends_on_the_preprocessor_only():
     """Records are sized per preprocessor (the frames they carry), not per task: the state rows are laid out with the
     same MG_MAX_* caps for a robot scene and a many-block scene."""
