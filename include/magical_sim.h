@@ -310,6 +310,56 @@ typedef struct {
 int mg_plan_cem(mg_sim *sim, uint8_t *actions_dev, uint16_t *weights_dev, int32_t warm,
                 int32_t H, int32_t K, int32_t iters, int32_t elites, int32_t alpha, int32_t repeat,
                 uint64_t key, uint64_t step, const mg_plan_cem_out *out, void *stream);
+/* Rollout objectives: what a rollout is worth, from the score and the reward after EVERY simulated env-step instead
+ * of the final state's score alone.  For env (or rollout) e with n = min(H, remaining) as mg_lookahead computes it,
+ * x_0 the state on entry and x_k the state after k env-steps:
+ *   s_k = score_on_end_of_traj(x_k), 0 <= k <= n;
+ *   done_k = max_episode_steps > 0 && episode_steps + k >= max_episode_steps, k >= 1 (it can hold at k = n only);
+ *   r_k, k >= 1 = the double mg_step casts to float for `reward` at that step: debug_reward(x_k) on a sim with the
+ *                 debug-reward flag, else done_k ? s_k : 0.0;
+ *   g_0 = 1.0, g_k = g_{k-1} * gamma (sequential products).
+ * Every operation below is one rounded IEEE double operation, none fused:
+ *   FINAL   value = s_n (mg_lookahead's score).
+ *   RETURN  G = 0.0; for k = 1..n: G = G + g_{k-1} * r_k; then, unless the episode ended inside the horizon (n >= 1 and
+ *           done_n): G = G + (g_n * tail) * s_n.  value = G.  tail = 0 is the plain truncated return; tail = 1 and
+ *           gamma = 1 without the debug reward is s_n exactly.
+ *   PEAK    P = s_0, kp = 0; for k = 1..n: v = g_k * s_k, and P = v, kp = k when v > P.  value = P: with gamma = 1 the
+ *           best score at any time in the horizon and kp when it was first reached; with gamma < 1 sooner is better. */
+enum { MG_OBJ_FINAL = 0, MG_OBJ_RETURN = 1, MG_OBJ_PEAK = 2 };
+typedef struct {
+    int32_t kind;      /* MG_OBJ_* */
+    int32_t reserved;  /* 0 */
+    double  gamma;     /* in (0, 1] */
+    double  tail;      /* finite, >= 0 */
+} mg_objective;
+/* Caller-owned device outputs, all NULL ok: */
+typedef struct {
+    double  *value;        /* f64[N]: the objective's value */
+    double  *peak;         /* f64[N]: P as defined above, with the objective's gamma, whatever the kind */
+    int32_t *peak_step;    /* i32[N]: kp */
+    double  *score_trace;  /* f64[H][N]: row h = s_{min(h+1, n)}; every element is written, none is NaN */
+    double  *reward_trace; /* f64[H][N]: row h = r_{h+1} for h < n, else 0.0; cast to float it is mg_step's reward */
+} mg_objective_out;
+/* mg_lookahead with an objective: `out` keeps its meaning for every kind (score is s_n) and the call is mg_lookahead in
+ * everything else -- the untouched sim, the scratch pool, the stream ordering, the H = 0 rules.  obj_out may be NULL
+ * (no objective outputs).  With kind FINAL and no objective output requested the call enqueues exactly what
+ * mg_lookahead does; otherwise the rollout kernel's traced form runs, which writes the env's state back to scratch
+ * and scores it after every env-step.
+ * Returns -22 and launches nothing for a null objective, a kind outside 0..2, reserved != 0, gamma outside (0, 1]
+ * (NaN included), a negative or non-finite tail, or anything mg_lookahead refuses.  gamma and tail are validated for
+ * FINAL too and otherwise ignored by it. */
+int mg_lookahead_obj(mg_sim *sim, const uint8_t *actions_dev, int32_t H, const mg_objective *objective,
+                     const mg_lookahead_out *out, const mg_objective_out *obj_out, void *stream);
+/* mg_plan / mg_plan_cem on an objective: scores, best_score and iter_best hold the objective's VALUE, and best, the
+ * elites and the incumbent are chosen on it; candidate k of env e is exactly mg_lookahead_obj of its action column
+ * (the same kernel on the fan pool).  Everything else, refusals included, is as in mg_plan / mg_plan_cem and as above
+ * for the objective; kind FINAL enqueues exactly what mg_plan / mg_plan_cem do.  No traces: mg_lookahead_obj on a
+ * column gives them. */
+int mg_plan_obj(mg_sim *sim, const uint8_t *actions_dev, int32_t H, int32_t K, const mg_objective *objective,
+                const mg_plan_out *out, void *stream);
+int mg_plan_cem_obj(mg_sim *sim, uint8_t *actions_dev, uint16_t *weights_dev, int32_t warm,
+                    int32_t H, int32_t K, int32_t iters, int32_t elites, int32_t alpha, int32_t repeat,
+                    uint64_t key, uint64_t step, const mg_objective *objective, const mg_plan_cem_out *out, void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

@@ -131,27 +131,28 @@ hipError_t mg_launch_cem_update(const CemUpdate &u, hipStream_t st) {
     return hipGetLastError();
 }
 
-extern "C" int mg_plan_cem(mg_sim *s, uint8_t *actions, uint16_t *weights, int32_t warm, int32_t H, int32_t K,
-                           int32_t iters, int32_t elites, int32_t alpha, int32_t repeat, uint64_t key, uint64_t step,
-                           const mg_plan_cem_out *out, void *stream) {
+// obj null: mg_plan_cem
+static int cem_run(mg_sim *s, const char *fn, uint8_t *actions, uint16_t *weights, int32_t warm, int32_t H, int32_t K,
+                   int32_t iters, int32_t elites, int32_t alpha, int32_t repeat, uint64_t key, uint64_t step,
+                   const mg_objective *obj, const mg_plan_cem_out *out, void *stream) {
+    const std::string f(fn);
     if (!s || !actions || !weights || !out || !out->best)
-        return set_err(-22, "mg_plan_cem: null sim, actions_dev, weights_dev, out or out->best");
-    if (H < 1 || H > 4096) return set_err(-22, "mg_plan_cem: H must be in [1, 4096]");
-    if (int rc = plan_check_sizes(s, "mg_plan_cem", H, K)) return rc;
-    if (iters < 1 || iters > 64) return set_err(-22, "mg_plan_cem: iters must be in [1, 64]");
-    if (elites < 1 || elites > K) return set_err(-22, "mg_plan_cem: elites must be in [1, K]");
-    if (alpha < 0 || alpha > 1024) return set_err(-22, "mg_plan_cem: alpha must be in [0, 1024]");
-    if (repeat < 1) return set_err(-22, "mg_plan_cem: repeat must be at least 1");
-    if (warm != 0 && warm != 1) return set_err(-22, "mg_plan_cem: warm must be 0 or 1");
+        return set_err(-22, f + ": null sim, actions_dev, weights_dev, out or out->best");
+    if (H < 1 || H > 4096) return set_err(-22, f + ": H must be in [1, 4096]");
+    if (int rc = plan_check_sizes(s, fn, H, K)) return rc;
+    if (iters < 1 || iters > 64) return set_err(-22, f + ": iters must be in [1, 64]");
+    if (elites < 1 || elites > K) return set_err(-22, f + ": elites must be in [1, K]");
+    if (alpha < 0 || alpha > 1024) return set_err(-22, f + ": alpha must be in [0, 1024]");
+    if (repeat < 1) return set_err(-22, f + ": repeat must be at least 1");
+    if (warm != 0 && warm != 1) return set_err(-22, f + ": warm must be 0 or 1");
     HIPC(hipSetDevice(s->device));
     const int n = s->main.S.n_envs, M = K * n, J = (H + repeat - 1) / repeat;
     RolloutPool &R = s->fan;
-    if (int rc = rollout_reserve(s, R, M, "mg_plan_cem")) return rc;
+    if (int rc = rollout_reserve(s, R, M, fn)) return rc;
     hipStream_t st = as_stream(stream);
     MGState F = R.P.S;
     F.n_envs = M;
     double *scores = out->scores ? out->scores : R.scores;
-    const LookOut lo = {scores, out->steps, nullptr, nullptr, out->errors};
     CemUpdate u = {actions, weights, scores, R.cem_thr, R.cem_kthr, out->best, n, H, K, J, repeat, alpha,
                    /*refit*/ 0, /*uniform*/ warm ? 0 : 1, /*draw*/ 1, /*incumbent*/ 0, key, step};
     HIPC(mg_launch_cem_update(u, st));   // iteration 0's candidates
@@ -159,7 +160,7 @@ extern "C" int mg_plan_cem(mg_sim *s, uint8_t *actions, uint16_t *weights, int32
     for (int i = 0; i < iters; i++) {
         const bool last = i == iters - 1;
         HIPC(mg_launch_plan_fan((const char *)s->main.mem, (char *)R.P.mem, R.rows, R.nrows, n, K, st));
-        HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+        if (int rc = plan_rollouts(s, F, actions, H, obj, scores, out->steps, out->errors, st)) return rc;
         double *bs = out->iter_best ? out->iter_best + (size_t)i * n : last ? out->best_score : nullptr;
         HIPC(mg_launch_plan_reduce(scores, actions, H, n, K, out->best, bs, out->first_action, st));
         if (last && out->iter_best && out->best_score)
@@ -171,4 +172,19 @@ extern "C" int mg_plan_cem(mg_sim *s, uint8_t *actions, uint16_t *weights, int32
         HIPC(mg_launch_cem_update(u, st));
     }
     return 0;
+}
+
+extern "C" int mg_plan_cem(mg_sim *s, uint8_t *actions, uint16_t *weights, int32_t warm, int32_t H, int32_t K,
+                           int32_t iters, int32_t elites, int32_t alpha, int32_t repeat, uint64_t key, uint64_t step,
+                           const mg_plan_cem_out *out, void *stream) {
+    return cem_run(s, "mg_plan_cem", actions, weights, warm, H, K, iters, elites, alpha, repeat, key, step, nullptr, out,
+                   stream);
+}
+
+extern "C" int mg_plan_cem_obj(mg_sim *s, uint8_t *actions, uint16_t *weights, int32_t warm, int32_t H, int32_t K,
+                               int32_t iters, int32_t elites, int32_t alpha, int32_t repeat, uint64_t key, uint64_t step,
+                               const mg_objective *obj, const mg_plan_cem_out *out, void *stream) {
+    if (int rc = objective_check(obj, "mg_plan_cem_obj")) return rc;
+    return cem_run(s, "mg_plan_cem_obj", actions, weights, warm, H, K, iters, elites, alpha, repeat, key, step, obj, out,
+                   stream);
 }

@@ -60,6 +60,24 @@ hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task,
                                 int H, const LookOut &out, hipStream_t st);
 hipError_t mg_launch_lookahead(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
                                const uint8_t *actions, int H, const LookOut &out, hipStream_t st);
+// mg_lookahead_obj / mg_plan_obj / mg_plan_cem_obj: the same rollout with the task's score s_k and mg_step's reward r_k
+// evaluated after every env-step k (the TRACE instantiation of the lookahead kernel, one per pair as above), and the
+// objective built on them (include/magical_sim.h: MG_OBJ_*).  The objective travels by value; the outputs are the
+// device pointers of mg_objective_out, all of which may be null -- and here LookOut.score may be null too (a plan's
+// [K][N] buffer receives `value` instead).  debug: the sim pays the dense debug reward (MG_DEBUG_REWARD).
+enum { LOOK_OBJ_FINAL = 0, LOOK_OBJ_RETURN = 1, LOOK_OBJ_PEAK = 2 };   // = MG_OBJ_* (checked in mg_lookahead.hip)
+struct LookObj {
+    int kind, debug;
+    double gamma, tail;
+    double *value, *peak;
+    int32_t *peak_step;
+    double *score_trace, *reward_trace;   // f64[H][n_envs], step-major as the actions
+};
+template <int VAR, int BLK>
+hipError_t launch_lookahead_obj_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
+                                    int H, const LookOut &out, const LookObj &obj, hipStream_t st);
+hipError_t mg_launch_lookahead_obj(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
+                                   const uint8_t *actions, int H, const LookOut &out, const LookObj &obj, hipStream_t st);
 hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderOut &ro, int mode, hipStream_t st);
 hipError_t mg_launch_compose3ea(const MGState &S, const uint8_t *obs_allo, const uint8_t *mask, uint8_t *obs_past,
                                 hipStream_t st);

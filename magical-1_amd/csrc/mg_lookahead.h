@@ -10,12 +10,20 @@
 // products, the robot's targets and motor rates -- is recomputed before use in every env-step, here as there).
 // What differs: the view is loaded once and written back once, S is the sim's scratch pool (never its own state),
 // and there is no episode counter, reward, done flag or reset -- only the outputs of LookOut.
+//
+// TRACE (mg_lookahead_obj, mg_plan_obj, mg_plan_cem_obj; a second instantiation of every pair): the env's view goes
+// back to its scratch column after EVERY env-step, as mg_step's does, and the env's scoring lane evaluates the task's
+// score s_k and mg_step's reward r_k there with score_env / debug_reward as they are -- the bits of mg_step's scoring
+// by construction -- and accumulates the objective (LookObj, mg_launch.h; the definitions: include/magical_sim.h and
+// DESIGN.md).  Everything TRACE adds is under `if constexpr (TRACE)`.
 #pragma once
 #include "mg_stepk.h"
 
-// the outputs (LookOut: mg_launch.h) of env e from the scratch state S after its n simulated env-steps (one lane per env)
+// the outputs (LookOut: mg_launch.h) of env e from the scratch state S after its n simulated env-steps (one lane per
+// env).  SCORE = false (TRACE): the caller has s_n already and stores it itself
+template <bool SCORE = true>
 MG_DEV void look_emit(const MGState &S, const mg_library *L, int e, int task, int n, const LookOut &o) {
-    o.score[e] = score_env(S, L, e, task);
+    if constexpr (SCORE) o.score[e] = score_env(S, L, e, task);
     if (o.steps) o.steps[e] = n;
     if (o.errors) o.errors[e] = S.overflow[e];
     if (o.bodies) {   // as bodies_kernel (mg_get_bodies)
@@ -33,11 +41,58 @@ MG_DEV void look_emit(const MGState &S, const mg_library *L, int e, int task, in
     }
 }
 
+// ---- TRACE: the objective's accumulators, in registers of the env's scoring lane --------------------------------
+// Every operation is one rounded double operation (no contraction: -ffp-contract=off), in the order of the
+// definitions: g_0 = 1, g_k = g_{k-1} * gamma; G += g_{k-1} * r_k; v = g_k * s_k, P = v and kp = k when v > P.
+struct ObjAcc {
+    double G, P, g, s;   // the return so far, the peak so far, g_k, s_k (k: env-steps done)
+    int kp;
+};
+
+// x_0: the scratch column as the fan-out copy left it (called before the env's first write-back)
+MG_DEV void obj_begin(ObjAcc &a, const MGState &S, const mg_library *L, int e, int task) {
+    a.s = score_env(S, L, e, task);
+    a.G = 0.0; a.P = a.s; a.g = 1.0; a.kp = 0;
+}
+
+// after env-step k = h + 1, with x_k in the scratch column (h < n <= H and e < n_envs: the trace index h * n_envs + e
+// lies inside f64[H][n_envs]); done: the step ends the episode, as mg_step decides it
+MG_DEV void obj_step(ObjAcc &a, const MGState &S, const mg_library *L, int e, int task, int h, bool done, const LookObj &o) {
+    const double s = score_env(S, L, e, task);
+    const double r = o.debug ? debug_reward(S, L, e, task) : done ? s : 0.0;   // the double mg_step casts to float
+    a.G = a.G + a.g * r;
+    a.g = a.g * o.gamma;
+    const double v = a.g * s;
+    if (v > a.P) { a.P = v; a.kp = h + 1; }
+    a.s = s;
+    const size_t i = (size_t)h * (size_t)S.n_envs + (size_t)e;
+    if (o.score_trace) o.score_trace[i] = s;
+    if (o.reward_trace) o.reward_trace[i] = r;
+}
+
+// the env's outputs after its n env-steps: LookOut as look_emit's (score = s_n), the objective's, and the trace rows
+// h in [n, H) (score clamped to s_n, reward 0)
+MG_DEV void obj_emit(const ObjAcc &a, const MGState &S, const mg_library *L, int e, int task, int n, int H, bool done_n,
+                     const LookOut &out, const LookObj &o) {
+    if (out.score) out.score[e] = a.s;
+    look_emit<false>(S, L, e, task, n, out);
+    double G = a.G;
+    if (!(n >= 1 && done_n)) G = G + (a.g * o.tail) * a.s;   // the episode goes on past the horizon: its tail value
+    if (o.value) o.value[e] = o.kind == LOOK_OBJ_RETURN ? G : o.kind == LOOK_OBJ_PEAK ? a.P : a.s;
+    if (o.peak) o.peak[e] = a.P;
+    if (o.peak_step) o.peak_step[e] = a.kp;
+    for (int h = n; h < H; h++) {
+        const size_t i = (size_t)h * (size_t)S.n_envs + (size_t)e;
+        if (o.score_trace) o.score_trace[i] = a.s;
+        if (o.reward_trace) o.reward_trace[i] = 0.0;
+    }
+}
+
 // S: the scratch pool, holding a copy of every env's state.  actions: u8[H][n_envs], step-major.  Env e runs
-// n = min(H, max_steps - episode_steps) env-steps (H when max_steps <= 0).
-template <int VAR, int BLK>
+// n = min(H, max_steps - episode_steps) env-steps (H when max_steps <= 0).  obj: read by TRACE only.
+template <int VAR, int BLK, bool TRACE = false>
 __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_library *__restrict__ L, int task, int max_steps,
-                                                       const uint8_t *__restrict__ actions, int H, LookOut out) {
+                                                       const uint8_t *__restrict__ actions, int H, LookOut out, LookObj obj) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr StepCaps C = step_form_caps(VAR);
     static_assert(mg_step_blk_ok(VAR, BLK), "not a pair of MG_STEP_FORMS (mg_stepforms.h)");
@@ -64,6 +119,16 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
         const int left = max_steps - S.episode_steps[e];
         n = left < 0 ? 0 : left < H ? left : H;
     }
+    // TRACE: env-step n ends the episode (mg_step: max_steps > 0 && episode_steps + n >= max_steps; n <= left, so
+    // no earlier step does).  The scoring lane -- the one lane of the env that reaches the outputs at the end -- holds
+    // the accumulators; it scores x_0 here, before anything is written to the env's scratch column (the first
+    // write-back lies behind the first env-step's barriers, which that lane takes part in)
+    [[maybe_unused]] bool done_n = false;
+    [[maybe_unused]] ObjAcc acc;
+    if constexpr (TRACE) {
+        done_n = max_steps > 0 && n >= 1 && S.episode_steps[e] + n >= max_steps;
+        if (!shadow && (COOP ? lane == 0 : sub == 0)) obj_begin(acc, S, L, e, task);
+    }
     MGProf P;
     MG_PP_INIT(P);
     if constexpr (LDS) {
@@ -80,7 +145,10 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
         for (int k = 0; k < S.nshapes[e] && k < C.ns && NCS > 0; k++) ok = ok && shape_body_slot(AT(S.sbody, k)); // arb_body
         if (!ok && fits && !shadow && sub == 0) S.overflow[e] |= 32; // the compiled constraint list does not describe this scene
         if (!QUAD && !(fits && ok)) {   // COOP, uniform over the workgroup: nothing is simulated
-            if (lane == 0) look_emit(S, L, e, task, 0, out);
+            if (lane == 0) {
+                if constexpr (TRACE) obj_emit(acc, S, L, e, task, 0, H, false, out, obj);
+                else look_emit(S, L, e, task, 0, out);
+            }
             return;
         }
         MGState V = S;
@@ -102,10 +170,27 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
             }
             for (int h = 0; h < hw; h++) {
                 env_substeps_quad<NCS, QL>(V, L, lane, sub, act[h * astride], P);   // ends with a workgroup barrier
-                // the env's last step: its column goes back to scratch from its own lanes, between that barrier and
-                // the next env-step's opening one (no lane writes the view there); afterwards the env goes on in LDS
-                // as a shadow does and never writes HBM again
-                if (own && h + 1 == n) xfer_state(S, V, C, lane, e, false, false, sub, QL);
+                if constexpr (TRACE) {
+                    // Every env-step of the env's own n: its column goes back to scratch from its own lanes, between
+                    // that closing barrier and the barrier below (no lane writes the view there: the next env-step
+                    // writes it only behind its opening barrier).  The fence and barrier publish the rows to the env's
+                    // sub-lane 0, which then scores from scratch -- HBM reads only, so the other lanes may run on into
+                    // the next env-step's opening barrier and wait there.  hw is uniform over the workgroup (the
+                    // butterfly above) and nothing returns or breaks inside the loop, so all 64 lanes -- shadows and
+                    // envs past their n included -- reach this barrier exactly hw times, as they do those of
+                    // env_substeps_quad.  An env past its n (and a shadow, n = 0) goes on in LDS and touches neither
+                    // its scratch column nor its outputs again: both are guarded by own && h < n, and h < n <= H,
+                    // e < n_envs bound the trace index (obj_step).
+                    if (own && h < n) xfer_state(S, V, C, lane, e, false, false, sub, QL);
+                    __threadfence_block();
+                    __syncthreads();
+                    if (own && sub == 0 && h < n) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);
+                } else {
+                    // the env's last step: its column goes back to scratch from its own lanes, between that barrier and
+                    // the next env-step's opening one (no lane writes the view there); afterwards the env goes on in LDS
+                    // as a shadow does and never writes HBM again
+                    if (own && h + 1 == n) xfer_state(S, V, C, lane, e, false, false, sub, QL);
+                }
             }
             // the env's lane 0 reads scratch rows its sibling lanes wrote back: ordered by the memory model (as
             // step_kernel)
@@ -115,25 +200,41 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
         } else {   // COOP
             xfer_state(S, V, C, 0, e, true, true, lane, 64);
             __syncthreads();
-            for (int h = 0; h < n; h++) env_substeps_coop(V, L, lane, act[h * astride], P);   // ends with a workgroup barrier
-            xfer_state(S, V, C, 0, e, false, true, lane, 64);
+            for (int h = 0; h < n; h++) {
+                env_substeps_coop(V, L, lane, act[h * astride], P);   // ends with a workgroup barrier
+                if constexpr (TRACE) {
+                    // all 64 lanes write the view back (n is uniform: one env per workgroup), fence and barrier, then
+                    // lane 0 scores from scratch.  It reads HBM only and the view is next written behind the next
+                    // env-step's first barrier, which waits for lane 0: no barrier is needed after the scoring
+                    xfer_state(S, V, C, 0, e, false, true, lane, 64);
+                    __threadfence_block();
+                    __syncthreads();
+                    if (lane == 0) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);
+                }
+            }
+            // (TRACE: the scratch holds x_n already -- the last step's write-back, or the untouched copy when n = 0)
+            if constexpr (!TRACE) xfer_state(S, V, C, 0, e, false, true, lane, 64);
             __threadfence_block();
             __syncthreads();
             if (lane != 0) return;
         }
     } else {
-        for (int h = 0; h < n; h++) env_substeps(S, L, e, act[h * astride], P);
+        for (int h = 0; h < n; h++) {
+            env_substeps(S, L, e, act[h * astride], P);
+            if constexpr (TRACE) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);   // form 0 steps S itself
+        }
     }
-    look_emit(S, L, e, task, n, out);
+    if constexpr (TRACE) obj_emit(acc, S, L, e, task, n, H, done_n, out, obj);
+    else look_emit(S, L, e, task, n, out);
 }
 
-template <int VAR, int BLK>
-hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
-                                int H, const LookOut &out, hipStream_t st) {
+template <int VAR, int BLK, bool TRACE>
+hipError_t launch_look(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions, int H,
+                       const LookOut &out, const LookObj &obj, hipStream_t st) {
     constexpr size_t lds = VAR == 0 ? 0 : mg_step_lds_bytes(step_form_caps(VAR), BLK);
     static bool attr_set = false;
     if (VAR != 0 && !attr_set) {
-        hipError_t err = hipFuncSetAttribute((const void *)lookahead_kernel<VAR, BLK>,
+        hipError_t err = hipFuncSetAttribute((const void *)lookahead_kernel<VAR, BLK, TRACE>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) {
             fprintf(stderr, "lookahead form %d/%d: LDS attribute %zu B: %s\n", VAR, BLK, lds, hipGetErrorString(err));
@@ -141,8 +242,8 @@ hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task,
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL((lookahead_kernel<VAR, BLK>), dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 0 ? BLK : 64), lds, st, S,
-                       L, task, max_steps, actions, H, out);
+    hipLaunchKernelGGL((lookahead_kernel<VAR, BLK, TRACE>), dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 0 ? BLK : 64), lds,
+                       st, S, L, task, max_steps, actions, H, out, obj);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
         fprintf(stderr, "lookahead form %d/%d: launch of %d workgroups, LDS %zu B: %s\n", VAR, BLK,
@@ -150,7 +251,21 @@ hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task,
     return err;
 }
 
-// a translation unit instantiates its row of the form table: MG_STEP_FORMS_QUAD(MG_LOOK_INSTANTIATE)
+template <int VAR, int BLK>
+hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
+                                int H, const LookOut &out, hipStream_t st) {
+    return launch_look<VAR, BLK, false>(S, L, task, max_steps, actions, H, out, LookObj{}, st);
+}
+
+template <int VAR, int BLK>
+hipError_t launch_lookahead_obj_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
+                                    int H, const LookOut &out, const LookObj &obj, hipStream_t st) {
+    return launch_look<VAR, BLK, true>(S, L, task, max_steps, actions, H, out, obj, st);
+}
+
+// a translation unit instantiates its row of the form table, plain and TRACE: MG_STEP_FORMS_QUAD(MG_LOOK_INSTANTIATE)
 #define MG_LOOK_INSTANTIATE(F, B) \
     template hipError_t launch_lookahead_var<F, B>(const MGState &, const mg_library *, int, int, const uint8_t *, int, \
-                                                   const LookOut &, hipStream_t);
+                                                   const LookOut &, hipStream_t); \
+    template hipError_t launch_lookahead_obj_var<F, B>(const MGState &, const mg_library *, int, int, const uint8_t *, \
+                                                       int, const LookOut &, const LookObj &, hipStream_t);

@@ -171,26 +171,53 @@ int rollout_reserve(mg_sim *s, RolloutPool &R, int M, const char *fn) {
     return 0;
 }
 
-extern "C" {
+int plan_rollouts(mg_sim *s, const MGState &F, const uint8_t *actions, int H, const mg_objective *obj, double *scores,
+                  int32_t *steps, int32_t *errors, hipStream_t st) {
+    if (!obj || obj->kind == MG_OBJ_FINAL) {
+        const LookOut lo = {scores, steps, nullptr, nullptr, errors};
+        HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+        return 0;
+    }
+    // the traced kernel with `value` pointed at the [K][N] scores and no s_n output
+    const LookOut lo = {nullptr, steps, nullptr, nullptr, errors};
+    LookObj a = objective_args(s, obj);
+    a.value = scores;
+    HIPC(mg_launch_lookahead_obj(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, a, st));
+    return 0;
+}
 
-int mg_plan(mg_sim *s, const uint8_t *actions, int32_t H, int32_t K, const mg_plan_out *out, void *stream) {
-    if (!s || !out || !out->best) return set_err(-22, "mg_plan: null sim, out or out->best");
-    if (int rc = plan_check_sizes(s, "mg_plan", H, K)) return rc;
-    if (!actions && H > 0) return set_err(-22, "mg_plan: null actions with H > 0");
+// obj null: mg_plan
+static int plan_run(mg_sim *s, const char *fn, const uint8_t *actions, int32_t H, int32_t K, const mg_objective *obj,
+                    const mg_plan_out *out, void *stream) {
+    const std::string f(fn);
+    if (!s || !out || !out->best) return set_err(-22, f + ": null sim, out or out->best");
+    if (int rc = plan_check_sizes(s, fn, H, K)) return rc;
+    if (!actions && H > 0) return set_err(-22, f + ": null actions with H > 0");
     HIPC(hipSetDevice(s->device));
     const int n = s->main.S.n_envs, M = K * n;
     RolloutPool &R = s->fan;
-    if (int rc = rollout_reserve(s, R, M, "mg_plan")) return rc;
+    if (int rc = rollout_reserve(s, R, M, fn)) return rc;
     hipStream_t st = as_stream(stream);
     // the pool may be larger than this call needs: its rows keep the stride it was laid out with, the launch covers M
     MGState F = R.P.S;
     F.n_envs = M;
     HIPC(mg_launch_plan_fan((const char *)s->main.mem, (char *)R.P.mem, R.rows, R.nrows, n, K, st));
     double *scores = out->scores ? out->scores : R.scores;
-    const LookOut lo = {scores, out->steps, nullptr, nullptr, out->errors};
-    HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+    if (int rc = plan_rollouts(s, F, actions, H, obj, scores, out->steps, out->errors, st)) return rc;
     HIPC(mg_launch_plan_reduce(scores, actions, H, n, K, out->best, out->best_score, out->first_action, st));
     return 0;
+}
+
+extern "C" {
+
+int mg_plan(mg_sim *s, const uint8_t *actions, int32_t H, int32_t K, const mg_plan_out *out, void *stream) {
+    return plan_run(s, "mg_plan", actions, H, K, nullptr, out, stream);
+}
+
+int mg_plan_obj(mg_sim *s, const uint8_t *actions, int32_t H, int32_t K, const mg_objective *obj, const mg_plan_out *out,
+                void *stream) {
+    if (int rc = objective_check(obj, "mg_plan_obj")) return rc;
+    return plan_run(s, "mg_plan_obj", actions, H, K, obj, out, stream);
 }
 
 int mg_plan_sample(mg_sim *s, uint8_t *actions, int32_t H, int32_t K, int32_t repeat, uint64_t key, uint64_t step,

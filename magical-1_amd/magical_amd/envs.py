@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import native, registry, spaces, tables
+from .planning import as_objective
 
 _LIBRARY = None
 
@@ -384,7 +385,12 @@ class VecMagicalEnv:
         native.check(self.lib.mg_restore(self.handle, ctypes.c_void_p(snap.blob.data_ptr()), ea, ra, n, self._stream()))
 
     # -- lookahead ---------------------------------------------------------------
-    def lookahead(self, actions, bodies=False):
+    def _objective_struct(self, objective, fn):
+        """the mg_objective of an `objective=` argument that is not None"""
+        o = as_objective(objective, fn)
+        return native.mg_objective(kind=o.kind_id, reserved=0, gamma=o.gamma, tail=o.tail)
+
+    def lookahead(self, actions, bodies=False, objective=None, trace=False):
         """What happens if these envs run these actions -- without touching them (mg_lookahead).  actions: [H, N]
         uint8 (tensor or array-like; [N] is H = 1; H = 0, an empty [0, N], scores the current states), step h of env e
         at actions[h, e].  Every env runs min(H, steps left in its episode) env-steps of physics only (no render, no
@@ -393,7 +399,13 @@ class VecMagicalEnv:
         episode ends inside the horizon), 'steps' i32[N] (env-steps simulated), 'errors' i32[N] (errors() as it
         would stand); with bodies=True also 'bodies' f64[N, 16, 6] and 'counts' i32[N, 4] of the final state, as
         bodies().  The env itself -- state, RNG, episode phase, frames, outputs -- is unchanged.  Enqueued on the
-        current stream; works with window=True and frames_only outputs."""
+        current stream; works with window=True and frames_only outputs.
+        objective (a magical_amd.Objective; mg_lookahead_obj) adds 'value' f64[N] (the objective's value of the
+        rollout), 'peak' f64[N] (the best discounted score at any step, the entry state included) and 'peak_step'
+        i32[N] (the first step that reached it; 0: the entry state).  trace=True adds 'score_trace' f64[H, N] (the
+        score after step h + 1, held at the final score past the env's last step) and 'reward_trace' f64[H, N] (the
+        reward step() would pay at step h + 1 before its cast to float32, 0 past the env's last step); without an
+        objective the traces are those of Objective('final').  With neither, nothing changes."""
         a = torch.as_tensor(actions)
         if a.dim() == 1:
             a = a[None]
@@ -408,8 +420,23 @@ class VecMagicalEnv:
             res["bodies"] = torch.empty((n, 16, 6), dtype=torch.float64, device=dev)
             res["counts"] = torch.empty((n, 4), dtype=torch.int32, device=dev)
         out = native.mg_lookahead_out(**{k: v.data_ptr() for k, v in res.items()})
-        native.check(self.lib.mg_lookahead(self.handle, ctypes.c_void_p(a.data_ptr()) if a.shape[0] else None,
-                                           int(a.shape[0]), ctypes.byref(out), self._stream()))
+        ap, H = ctypes.c_void_p(a.data_ptr()) if a.shape[0] else None, int(a.shape[0])
+        if objective is None and not trace:
+            native.check(self.lib.mg_lookahead(self.handle, ap, H, ctypes.byref(out), self._stream()))
+        else:
+            obj = self._objective_struct("final" if objective is None else objective, "lookahead")
+            extra = collections.OrderedDict()
+            if objective is not None:
+                extra["value"] = torch.empty(n, dtype=torch.float64, device=dev)
+                extra["peak"] = torch.empty(n, dtype=torch.float64, device=dev)
+                extra["peak_step"] = torch.empty(n, dtype=torch.int32, device=dev)
+            if trace:
+                extra["score_trace"] = torch.empty((H, n), dtype=torch.float64, device=dev)
+                extra["reward_trace"] = torch.empty((H, n), dtype=torch.float64, device=dev)
+            oo = native.mg_objective_out(**{k: v.data_ptr() for k, v in extra.items() if v.numel()})
+            native.check(self.lib.mg_lookahead_obj(self.handle, ap, H, ctypes.byref(obj), ctypes.byref(out),
+                                                   ctypes.byref(oo), self._stream()))
+            res.update(extra)
         self._last_lookahead = a   # (alive until the next call: the kernel reads it on the stream)
         return res
 
@@ -419,7 +446,7 @@ class VecMagicalEnv:
         return self.lookahead(torch.empty((0, self.num_envs), dtype=torch.uint8))["score"]
 
     # -- planning ----------------------------------------------------------------
-    def plan(self, actions, details=False):
+    def plan(self, actions, details=False, objective=None):
         """Which of K candidate action sequences is best for each env -- without touching the envs (mg_plan).
         actions: [H, K, N] uint8 (tensor or array-like; [K, N] is H = 1; an empty [0, K, N] scores the current states K
         times), step h of candidate k of env e at actions[h, k, e].  Candidate k of env e is exactly
@@ -428,7 +455,9 @@ class VecMagicalEnv:
         f64[N], 'first_action' u8[N] (actions[0, best[e], e]; zeros when H = 0); with details=True also 'scores'
         f64[K, N], 'steps' i32[K, N] and 'errors' i32[K, N] as lookahead's.  Error flags do not exclude a candidate.
         Enqueued on the current stream, except that a call needing a larger fan pool than the last allocates it and
-        synchronises the device."""
+        synchronises the device.
+        objective (a magical_amd.Objective; mg_plan_obj): 'scores' and 'best_score' hold the objective's value --
+        lookahead(actions[:, k], objective=objective)['value'] -- and 'best' is chosen on it."""
         a = plan_actions(actions, self.num_envs).to(self.device).contiguous()
         H, K, n, dev = int(a.shape[0]), int(a.shape[1]), self.num_envs, self.device
         res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
@@ -439,8 +468,12 @@ class VecMagicalEnv:
             res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
             res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
         out = native.mg_plan_out(**{k: v.data_ptr() for k, v in res.items()})
-        native.check(self.lib.mg_plan(self.handle, ctypes.c_void_p(a.data_ptr()) if H else None, H, K, ctypes.byref(out),
-                                      self._stream()))
+        ap = ctypes.c_void_p(a.data_ptr()) if H else None
+        if objective is None:
+            native.check(self.lib.mg_plan(self.handle, ap, H, K, ctypes.byref(out), self._stream()))
+        else:
+            obj = self._objective_struct(objective, "plan")
+            native.check(self.lib.mg_plan_obj(self.handle, ap, H, K, ctypes.byref(obj), ctypes.byref(out), self._stream()))
         self._last_plan = a   # (alive until the next call: the kernels read it on the stream)
         return res
 
@@ -459,7 +492,8 @@ class VecMagicalEnv:
                                              int(step), self._stream()))
         return out
 
-    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False):
+    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False,
+                 objective=None):
         """Cross-entropy planning on the device (mg_plan_cem): `iters` rounds of K candidate sequences of H env-steps
         per env (each action held for `repeat` steps, J = ceil(H / repeat) slots), every round rolled out as plan()
         does, the per-env, per-slot action weights refitted to its `elites` best candidates (alpha + elite counts)
@@ -469,7 +503,10 @@ class VecMagicalEnv:
         tensors: 'best' i32[N] (index into the last round's candidates), 'best_score' f64[N], 'first_action' u8[N],
         'plan' u8[H, N] (the best sequence), 'weights' u16[J, 18, N] (the given tensor when one was given),
         'iter_best' f64[iters, N]; with details=True also 'actions' u8[H, K, N] (the last round's candidates) and
-        their 'scores' f64[K, N], 'steps' i32[K, N], 'errors' i32[K, N].  The envs are untouched, as by plan()."""
+        their 'scores' f64[K, N], 'steps' i32[K, N], 'errors' i32[K, N].  The envs are untouched, as by plan().
+        objective (a magical_amd.Objective; mg_plan_cem_obj): every round is plan(objective=objective), so the scores,
+        'best_score' and 'iter_best' are the objective's values and the elites and the incumbent are chosen on them."""
+        obj = None if objective is None else self._objective_struct(objective, "plan_cem")
         H, K, iters, repeat, n, dev = int(H), int(K), int(iters), int(repeat), self.num_envs, self.device
         if H < 1 or K < 1 or iters < 1 or repeat < 1:
             raise ValueError("plan_cem: H, K, iters and repeat must be at least 1")
@@ -492,9 +529,12 @@ class VecMagicalEnv:
             res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
             res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
         out = native.mg_plan_cem_out(**{k: v.data_ptr() for k, v in res.items()})
-        native.check(self.lib.mg_plan_cem(self.handle, ctypes.c_void_p(acts.data_ptr()), ctypes.c_void_p(weights.data_ptr()),
-                                          int(warm), H, K, iters, int(elites), int(alpha), repeat, int(key), int(step),
-                                          ctypes.byref(out), self._stream()))
+        args = (self.handle, ctypes.c_void_p(acts.data_ptr()), ctypes.c_void_p(weights.data_ptr()), int(warm), H, K, iters,
+                int(elites), int(alpha), repeat, int(key), int(step))
+        if obj is None:
+            native.check(self.lib.mg_plan_cem(*args, ctypes.byref(out), self._stream()))
+        else:
+            native.check(self.lib.mg_plan_cem_obj(*args, ctypes.byref(obj), ctypes.byref(out), self._stream()))
         plan = acts.gather(1, res["best"].long()[None, None, :].expand(H, 1, n))[:, 0]
         ordered = collections.OrderedDict([(k, res[k]) for k in ("best", "best_score", "first_action")])
         ordered["plan"], ordered["weights"], ordered["iter_best"] = plan, weights, res["iter_best"]
@@ -580,33 +620,50 @@ class MagicalEnv:
             raise RuntimeError("call reset() before score()")
         return float(self._vec.score()[0].item())
 
-    def lookahead(self, actions):
+    def lookahead(self, actions, objective=None, trace=False):
         """Score of the state after running `actions` (a sequence of action ids, cut at the episode's end) from the
-        current state, which stays as it is: (score, env-steps simulated)."""
+        current state, which stays as it is: (score, env-steps simulated).  With an objective (a
+        magical_amd.Objective) or trace=True the result is a dict instead: 'score' and 'steps' as above, with an
+        objective 'value', 'peak' (floats) and 'peak_step' (int), with trace=True 'score_trace' and 'reward_trace'
+        as float64 arrays [H] (VecMagicalEnv.lookahead for this one env)."""
         if self._episode_steps is None:
             raise RuntimeError("call reset() before lookahead()")
-        res = self._vec.lookahead(torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1))
-        return float(res["score"][0].item()), int(res["steps"][0].item())
+        a = torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1)
+        if objective is None and not trace:
+            res = self._vec.lookahead(a)
+            return float(res["score"][0].item()), int(res["steps"][0].item())
+        res = self._vec.lookahead(a, objective=objective, trace=trace)
+        out = {"score": float(res["score"][0].item()), "steps": int(res["steps"][0].item())}
+        if objective is not None:
+            out.update(value=float(res["value"][0].item()), peak=float(res["peak"][0].item()),
+                       peak_step=int(res["peak_step"][0].item()))
+        if trace:
+            out.update(score_trace=res["score_trace"][:, 0].cpu().numpy(), reward_trace=res["reward_trace"][:, 0].cpu().numpy())
+        return out
 
-    def plan(self, actions):
+    def plan(self, actions, objective=None):
         """The best of K candidate action sequences from the current state, which stays as it is.  actions: [H, K]
         action ids (candidate k is the column actions[:, k]).  Returns (best, best_score, scores): the index of the
-        highest-scoring candidate (the lowest on ties), its score, and every candidate's score as a float64 array [K]."""
+        highest-scoring candidate (the lowest on ties), its score, and every candidate's score as a float64 array [K].
+        With an objective (a magical_amd.Objective) the scores are its values and the best is chosen on them."""
         if self._episode_steps is None:
             raise RuntimeError("call reset() before plan()")
         a = torch.as_tensor(np.asarray(actions), dtype=torch.uint8)
         if a.dim() != 2:
             raise ValueError(f"plan: actions must be [H, K], got {tuple(a.shape)}")
-        res = self._vec.plan(a[:, :, None], details=True)
+        kw = {} if objective is None else {"objective": objective}
+        res = self._vec.plan(a[:, :, None], details=True, **kw)
         return int(res["best"][0].item()), float(res["best_score"][0].item()), res["scores"][:, 0].cpu().numpy()
 
-    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0):
+    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, objective=None):
         """Cross-entropy planning from the current state, which stays as it is (VecMagicalEnv.plan_cem for this one
         env, from uniform weights).  Returns (plan, best_score, iter_best): the best action sequence found as a
-        uint8 array [H], its score, and the best score of every iteration as a float64 array [iters]."""
+        uint8 array [H], its score, and the best score of every iteration as a float64 array [iters].  With an
+        objective (a magical_amd.Objective) the scores are its values."""
         if self._episode_steps is None:
             raise RuntimeError("call reset() before plan_cem()")
-        res = self._vec.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key, step=step)
+        kw = {} if objective is None else {"objective": objective}
+        res = self._vec.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key, step=step, **kw)
         return res["plan"][:, 0].cpu().numpy(), float(res["best_score"][0].item()), res["iter_best"][:, 0].cpu().numpy()
 
     def get_state(self):

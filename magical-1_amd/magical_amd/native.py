@@ -16,8 +16,9 @@ EXPORTS = ["mg_create", "mg_bind_outputs", "mg_reset", "mg_step", "mg_render_ful
            "mg_set_body_pose", "mg_get_errors", "mg_seed", "mg_random_actions", "mg_num_envs", "mg_step_form", "mg_enable_timing", "mg_read_timing",
            "mg_set_episode_steps", "mg_selftest_sincos", "mg_replay_lores", "mg_restack", "mg_restack_window", "mg_bind_window",
            "mg_window_start", "mg_snapshot_bytes", "mg_snapshot", "mg_restore", "mg_lookahead", "mg_plan", "mg_plan_sample",
-           "mg_plan_cem", "mg_destroy", "mg_last_error"]
+           "mg_plan_cem", "mg_lookahead_obj", "mg_plan_obj", "mg_plan_cem_obj", "mg_destroy", "mg_last_error"]
 PLAN_MAX_ROLLOUTS = 262144   # MG_PLAN_MAX_ROLLOUTS: K * num_envs of one mg_plan call
+OBJ_FINAL, OBJ_RETURN, OBJ_PEAK = 0, 1, 2   # MG_OBJ_*
 
 
 class mg_config(ctypes.Structure):
@@ -48,6 +49,16 @@ class mg_plan_cem_out(ctypes.Structure):
     _fields_ = [("best", ctypes.c_void_p), ("best_score", ctypes.c_void_p), ("first_action", ctypes.c_void_p),
                 ("scores", ctypes.c_void_p), ("steps", ctypes.c_void_p), ("errors", ctypes.c_void_p),
                 ("iter_best", ctypes.c_void_p)]
+
+
+class mg_objective(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("gamma", ctypes.c_double),
+                ("tail", ctypes.c_double)]
+
+
+class mg_objective_out(ctypes.Structure):
+    _fields_ = [("value", ctypes.c_void_p), ("peak", ctypes.c_void_p), ("peak_step", ctypes.c_void_p),
+                ("score_trace", ctypes.c_void_p), ("reward_trace", ctypes.c_void_p)]
 
 
 class NativeError(RuntimeError):
@@ -114,6 +125,11 @@ def load():
     lib.mg_plan_sample.argtypes = [vp, vp, i32, i32, i32, u64, u64, vp]
     lib.mg_plan_cem.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, u64, u64,
                                 ctypes.POINTER(mg_plan_cem_out), vp]
+    po = ctypes.POINTER(mg_objective)
+    lib.mg_lookahead_obj.argtypes = [vp, vp, i32, po, ctypes.POINTER(mg_lookahead_out), ctypes.POINTER(mg_objective_out), vp]
+    lib.mg_plan_obj.argtypes = [vp, vp, i32, i32, po, ctypes.POINTER(mg_plan_out), vp]
+    lib.mg_plan_cem_obj.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, u64, u64, po,
+                                    ctypes.POINTER(mg_plan_cem_out), vp]
     lib.mg_destroy.argtypes = [vp]
     lib.mg_destroy.restype = None
     lib.mg_last_error.restype = ctypes.c_char_p

@@ -214,10 +214,12 @@ class PipelinedVecEnv:
         self._last = []
         return self._obs()
 
-    def lookahead(self, actions, bodies=False):
+    def lookahead(self, actions, bodies=False, objective=None, trace=False):
         """VecMagicalEnv.lookahead for the whole pool: actions [H, num_envs] ([num_envs]: H = 1); chunk k runs its
         columns [bounds[k], bounds[k + 1]) on its own stream once every chunk's last step is done, and the results
-        are concatenated in env order (complete: the caller's stream is ordered after the chunks)."""
+        are concatenated in env order (complete: the caller's stream is ordered after the chunks).  objective and
+        trace as VecMagicalEnv.lookahead's, per chunk."""
+        kw = {} if objective is None and not trace else {"objective": objective, "trace": trace}
         a = torch.as_tensor(actions)
         if a.dim() == 1:
             a = a[None]
@@ -229,27 +231,29 @@ class PipelinedVecEnv:
         b, parts = self.bounds, []
         for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
             with torch.cuda.stream(st):   # a column slice is strided: the chunk gets its own contiguous [H, m] copy
-                parts.append(sim.lookahead(a[:, b[k]:b[k + 1]].contiguous(), bodies=bodies))
+                parts.append(sim.lookahead(a[:, b[k]:b[k + 1]].contiguous(), bodies=bodies, **kw))
         self.wait()
         out = collections.OrderedDict()
-        for key in parts[0]:
-            out[key] = torch.cat([p[key] for p in parts])
+        for key in parts[0]:   # envs are the first axis of every result but the [H, m] traces
+            out[key] = torch.cat([p[key] for p in parts], dim=-1 if key.endswith("_trace") else 0)
             for p in parts:   # allocated on the chunks' streams, read here on the caller's
                 p[key].record_stream(self._caller())
         return out
 
-    def plan(self, actions, details=False):
+    def plan(self, actions, details=False, objective=None):
         """VecMagicalEnv.plan for the whole pool: actions [H, K, num_envs] ([K, num_envs]: H = 1); chunk k plans its
         envs [bounds[k], bounds[k + 1]) on its own stream once every chunk's last step is done, and the results are
-        concatenated in env order (complete: the caller's stream is ordered after the chunks)."""
+        concatenated in env order (complete: the caller's stream is ordered after the chunks).  objective as
+        VecMagicalEnv.plan's."""
         from .envs import plan_actions
+        kw = {} if objective is None else {"objective": objective}
         a = plan_actions(actions, self.num_envs).to(self.device)
         self.wait()
         self._fork()
         b, parts = self.bounds, []
         for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
             with torch.cuda.stream(st):   # an env slice is strided: the chunk gets its own contiguous [H, K, m] copy
-                parts.append(sim.plan(a[:, :, b[k]:b[k + 1]].contiguous(), details=details))
+                parts.append(sim.plan(a[:, :, b[k]:b[k + 1]].contiguous(), details=details, **kw))
         self.wait()
         out = collections.OrderedDict()
         for key in parts[0]:
@@ -272,11 +276,14 @@ class PipelinedVecEnv:
             out[:, :, b[k]:b[k + 1]] = sim.sample_plans(H, K, repeat=repeat, key=key + k, step=step)
         return out
 
-    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False):
+    def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False,
+                 objective=None):
         """VecMagicalEnv.plan_cem for the whole pool: chunk k plans its envs [bounds[k], bounds[k + 1]) on its own
         stream with key + k (envs numbered from 0, as sample_plans), and the results are concatenated in env order.
         weights: None, or a uint16 [J, 18, num_envs] tensor on the pool's device, the warm start, updated in place
-        (each chunk works on its own contiguous copy of its columns, which is copied back)."""
+        (each chunk works on its own contiguous copy of its columns, which is copied back).  objective as
+        VecMagicalEnv.plan_cem's."""
+        kw = {} if objective is None else {"objective": objective}
         J = -(-int(H) // max(int(repeat), 1))
         if weights is not None and (not torch.is_tensor(weights) or tuple(weights.shape) != (J, 18, self.num_envs)
                                     or weights.dtype != torch.uint16 or weights.device != self.device):
@@ -289,7 +296,7 @@ class PipelinedVecEnv:
                 w = (None if weights is None
                      else weights.view(torch.int16)[:, :, b[k]:b[k + 1]].contiguous().view(torch.uint16))
                 parts.append(sim.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key + k, step=step,
-                                          weights=w, details=details))
+                                          weights=w, details=details, **kw))
         self.wait()
         out = collections.OrderedDict()
         for name in parts[0]:

@@ -4,7 +4,68 @@
 action sequences of H env-steps per env (sample_plans), rolls all of them out from the envs' current states without
 touching them (plan), and plays the first action of each env's best sequence.  The candidates come from the device
 generator, so a run is a function of (key, the envs' states) alone.
+
+Every planner takes an `Objective`: what a rollout is worth.  The default, the score of the rollout's final state, is
+blind to a goal that was crossed and left again and ignores the env's dense reward; `Objective("return")` is the
+discounted sum of the rewards step() would pay over the horizon (plus `tail` times the discounted final score when the
+episode goes on past it), `Objective("peak")` the best discounted score at any step of the horizon.
 """
+import math
+
+OBJECTIVE_KINDS = {"final": 0, "return": 1, "peak": 2}   # MG_OBJ_* (include/magical_sim.h)
+
+
+class Objective:
+    """What a rollout is worth (mg_objective): kind 'final' (the final state's score s_n), 'return' (sum over the
+    simulated steps k of gamma^(k-1) * reward_k, plus tail * gamma^n * s_n unless the episode ended inside the horizon)
+    or 'peak' (max over k of gamma^k * s_k, the entry state included).  gamma in (0, 1]; tail finite and >= 0.  An
+    immutable value: equal fields compare equal."""
+
+    __slots__ = ("kind", "gamma", "tail")
+
+    def __init__(self, kind="final", gamma=1.0, tail=0.0):
+        if kind not in OBJECTIVE_KINDS:
+            raise ValueError(f"Objective: kind must be one of {sorted(OBJECTIVE_KINDS)}, got {kind!r}")
+        try:
+            gamma, tail = float(gamma), float(tail)
+        except (TypeError, ValueError):
+            raise ValueError("Objective: gamma and tail must be numbers") from None
+        if not 0.0 < gamma <= 1.0:
+            raise ValueError(f"Objective: gamma must be in (0, 1], got {gamma}")
+        if not (math.isfinite(tail) and tail >= 0.0):
+            raise ValueError(f"Objective: tail must be finite and not negative, got {tail}")
+        object.__setattr__(self, "kind", kind)
+        object.__setattr__(self, "gamma", gamma)
+        object.__setattr__(self, "tail", tail)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Objective is immutable")
+
+    @property
+    def kind_id(self):
+        return OBJECTIVE_KINDS[self.kind]
+
+    def _key(self):
+        return (self.kind, self.gamma, self.tail)
+
+    def __eq__(self, other):
+        return isinstance(other, Objective) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Objective(kind={self.kind!r}, gamma={self.gamma!r}, tail={self.tail!r})"
+
+
+def as_objective(objective, fn):
+    """None or an Objective, for the `objective=` argument of fn; anything else is a ValueError (a kind name is
+    accepted as shorthand for Objective(kind))."""
+    if objective is None or isinstance(objective, Objective):
+        return objective
+    if isinstance(objective, str):
+        return Objective(objective)
+    raise ValueError(f"{fn}: objective must be None, a kind name or a magical_amd.Objective, got {type(objective).__name__}")
 
 
 def plan_step(t, horizon, candidates, repeat=1):
@@ -33,9 +94,11 @@ class CEMPolicy:
     env-steps, refitted to the `elites` best with smoothing count `alpha`, and plays the first action of each env's
     best sequence.  Decision t draws from counter cem_step(t, ...) on.  warm_start=True (repeat == 1 only: a slot is
     then one env-step) carries the fitted weights to the next decision, shifted one slot towards the present with the
-    last slot reset to all ones; reset() drops them and starts the decision counter again."""
+    last slot reset to all ones; reset() drops them and starts the decision counter again.  objective: the Objective
+    the candidates are ranked by (None: the final state's score, plan_cem() as it always was)."""
 
-    def __init__(self, env, horizon, candidates, iters, elites, alpha=1, repeat=1, key=42, warm_start=False):
+    def __init__(self, env, horizon, candidates, iters, elites, alpha=1, repeat=1, key=42, warm_start=False,
+                 objective=None):
         if int(horizon) < 1 or int(candidates) < 1 or int(iters) < 1 or int(repeat) < 1:
             raise ValueError("CEMPolicy: horizon, candidates, iters and repeat must be at least 1")
         if not 1 <= int(elites) <= int(candidates):
@@ -46,6 +109,7 @@ class CEMPolicy:
             raise ValueError("CEMPolicy: warm_start needs repeat == 1 (the weights are shifted by one env-step)")
         self.env, self.horizon, self.candidates, self.iters = env, int(horizon), int(candidates), int(iters)
         self.elites, self.alpha, self.repeat, self.key, self.warm_start = int(elites), int(alpha), int(repeat), key, bool(warm_start)
+        self.objective = as_objective(objective, "CEMPolicy")
         self.t = 0
         self.weights = None   # warm_start: the next decision's starting weights
         self.last = None      # the latest decision's plan_cem() result
@@ -55,9 +119,10 @@ class CEMPolicy:
         self.weights = None
 
     def __call__(self, obs=None):
+        kw = {} if self.objective is None else {"objective": self.objective}
         self.last = self.env.plan_cem(self.horizon, self.candidates, self.iters, self.elites, alpha=self.alpha,
                                       repeat=self.repeat, key=self.key, weights=self.weights,
-                                      step=cem_step(self.t, self.horizon, self.candidates, self.iters, self.repeat))
+                                      step=cem_step(self.t, self.horizon, self.candidates, self.iters, self.repeat), **kw)
         if self.warm_start:
             self.weights = shift_weights(self.last["weights"])
         self.t += 1
@@ -70,12 +135,14 @@ class ShootingPolicy:
     The observation is not used -- the plan starts from the env's state -- so the policy fits
     BatchedEvaluationProtocol's policy(obs_dict) contract when it wraps the env being evaluated, and a plain
     reset() / step() loop.  reset() starts the decision counter again: two runs with the same key over the same env
-    states give the same actions."""
+    states give the same actions.  objective: the Objective the candidates are ranked by (None: the final state's
+    score, plan() as it always was)."""
 
-    def __init__(self, env, horizon, candidates, repeat=1, key=42):
+    def __init__(self, env, horizon, candidates, repeat=1, key=42, objective=None):
         if int(horizon) < 1 or int(candidates) < 1 or int(repeat) < 1:
             raise ValueError("ShootingPolicy: horizon, candidates and repeat must be at least 1")
         self.env, self.horizon, self.candidates, self.repeat, self.key = env, int(horizon), int(candidates), int(repeat), key
+        self.objective = as_objective(objective, "ShootingPolicy")
         self.t = 0
         self.last = None   # the latest decision's plan() result
 
@@ -85,6 +152,6 @@ class ShootingPolicy:
     def __call__(self, obs=None):
         acts = self.env.sample_plans(self.horizon, self.candidates, self.repeat, self.key,
                                      step=plan_step(self.t, self.horizon, self.candidates, self.repeat))
-        self.last = self.env.plan(acts)
+        self.last = self.env.plan(acts) if self.objective is None else self.env.plan(acts, objective=self.objective)
         self.t += 1
         return self.last["first_action"]

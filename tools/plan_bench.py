@@ -35,6 +35,60 @@ sys.path.insert(0, os.path.join(ROOT, "magical-1_amd"))
 from magical_amd import envs as mg_envs, native  # noqa: E402
 
 
+def objective_bench(args, env, ks, timed, stats, res):
+    """--objective: for every K, each repetition times in turn mg_plan, mg_plan_obj with FINAL (the same kernels),
+    RETURN (tail 1) and PEAK (the traced rollout kernel: a write-back and a score per env-step), and H mg_step calls of
+    a second sim of K * N envs under mg_enable_timing, whose out[0] is the step kernel alone: the yardstick for a
+    rollout that writes back and scores every step, as mg_step does.  Adds to res["K"][K] the medians with min / max
+    and each route's ratio to mg_plan and to the step kernels."""
+    lib, dev, st, n, H = env.lib, env.device, env._stream(), env.num_envs, args.horizon
+    routes = {"plan": None, "final": native.mg_objective(kind=native.OBJ_FINAL, gamma=1.0, tail=0.0),
+              "return": native.mg_objective(kind=native.OBJ_RETURN, gamma=args.gamma, tail=1.0),
+              "peak": native.mg_objective(kind=native.OBJ_PEAK, gamma=args.gamma, tail=0.0)}
+    for K in ks:
+        acts = env.sample_plans(H, K, key=77, step=1000)
+        best = torch.empty(n, dtype=torch.int32, device=dev)
+        score = torch.empty(n, dtype=torch.float64, device=dev)
+        scores = torch.empty((K, n), dtype=torch.float64, device=dev)
+        out = native.mg_plan_out(best=best.data_ptr(), best_score=score.data_ptr(), scores=scores.data_ptr())
+        ap_ = ctypes.c_void_p(acts.data_ptr())
+
+        def run(obj):
+            if obj is None:
+                native.check(lib.mg_plan(env.handle, ap_, H, K, ctypes.byref(out), st))
+            else:
+                native.check(lib.mg_plan_obj(env.handle, ap_, H, K, ctypes.byref(obj), ctypes.byref(out), st))
+
+        run(None)
+        ref = scores.clone()
+        run(routes["final"])
+        torch.cuda.synchronize()
+        assert torch.equal(scores, ref)
+        big = mg_envs.VecMagicalEnv(args.name, K * n, max_episode_steps=10 ** 6)
+        big.reset()
+        big_acts = [big.random_actions(t) for t in range(H)]
+        tm = (ctypes.c_double * 4)()
+        t = {key: [] for key in list(routes) + ["step_kernel_x_H"]}
+        for rep in range(args.warmup + args.reps):
+            row = {key: timed(lambda o=obj: run(o)) for key, obj in routes.items()}
+            native.check(lib.mg_enable_timing(big.handle, H))
+            for h in range(H):
+                big.step(big_acts[h])
+            torch.cuda.synchronize()
+            native.check(lib.mg_read_timing(big.handle, tm))
+            native.check(lib.mg_enable_timing(big.handle, 0))
+            row["step_kernel_x_H"] = tm[0]
+            if rep >= args.warmup:
+                for key, v in row.items():
+                    t[key].append(v)
+        big.close()
+        med = {key: statistics.median(v) for key, v in t.items()}
+        res["K"][str(K)] = dict({key: stats(v) for key, v in t.items()},
+                                over_plan={key: round(med[key] / med["plan"], 3) for key in ("final", "return", "peak")},
+                                over_step_kernels={key: round(med[key] / med["step_kernel_x_H"], 3)
+                                                   for key in ("plan", "return", "peak")})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--name", default="MoveToRegion-Demo-LoRes4E-v0")
@@ -44,6 +98,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=20, help="env steps before the first measurement")
+    ap.add_argument("--objective", action="store_true",
+                    help="time mg_plan against mg_plan_obj with FINAL, RETURN and PEAK instead (see objective_bench)")
+    ap.add_argument("--gamma", type=float, default=0.99, help="--objective: the discount of RETURN and PEAK")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("plan_bench: no GPU (times are measured on the device or not at all)")
@@ -67,6 +124,11 @@ def main():
         return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
     res = {"name": args.name, "envs": n, "step_form": list(env.step_form()[:2]), "H": H, "reps": args.reps, "K": {}}
+    if args.objective:
+        objective_bench(args, env, ks, timed, stats, res)
+        print(json.dumps(res))
+        env.close()
+        return
     free0 = torch.cuda.mem_get_info(dev)[0]
     env.plan(env.sample_plans(1, max(ks)))   # the fan pool for the largest K: later calls allocate nothing
     torch.cuda.synchronize()
