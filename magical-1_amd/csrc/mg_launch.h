@@ -55,11 +55,6 @@ hipError_t mg_launch_step(const MGState &S, const mg_library *L, TaskCfg cfg, in
 // device pointers of mg_lookahead_out; score is never null).  actions: u8[H][n_envs].  One compiled pair per pair of
 // the step kernel (defined in mg_lookahead.h, instantiated in mg_look_*.hip, dispatched in mg_lookahead.hip)
 struct LookOut { double *score; int32_t *steps; double *bodies; int32_t *counts; int32_t *errors; };
-template <int VAR, int BLK>
-hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
-                                int H, const LookOut &out, hipStream_t st);
-hipError_t mg_launch_lookahead(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
-                               const uint8_t *actions, int H, const LookOut &out, hipStream_t st);
 // mg_lookahead_obj / mg_plan_obj / mg_plan_cem_obj: the same rollout with the task's score s_k and mg_step's reward r_k
 // evaluated after every env-step k (the TRACE instantiation of the lookahead kernel, one per pair as above), and the
 // objective built on them (include/magical_sim.h: MG_OBJ_*).  The objective travels by value; the outputs are the
@@ -73,11 +68,13 @@ struct LookObj {
     int32_t *peak_step;
     double *score_trace, *reward_trace;   // f64[H][n_envs], step-major as the actions
 };
-template <int VAR, int BLK>
-hipError_t launch_lookahead_obj_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
-                                    int H, const LookOut &out, const LookObj &obj, hipStream_t st);
-hipError_t mg_launch_lookahead_obj(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
-                                   const uint8_t *actions, int H, const LookOut &out, const LookObj &obj, hipStream_t st);
+// one compiled lookahead kernel: a pair as above, plain (obj is not read) or TRACE
+template <int VAR, int BLK, bool TRACE>
+hipError_t launch_look(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions, int H,
+                       const LookOut &out, const LookObj &obj, hipStream_t st);
+// obj null: the plain kernel; else the TRACE one
+hipError_t mg_launch_lookahead(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
+                               const uint8_t *actions, int H, const LookOut &out, const LookObj *obj, hipStream_t st);
 hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderOut &ro, int mode, hipStream_t st);
 hipError_t mg_launch_compose3ea(const MGState &S, const uint8_t *obs_allo, const uint8_t *mask, uint8_t *obs_past,
                                 hipStream_t st);

@@ -3,12 +3,14 @@
 // step kernel's table (mg_stepforms.h), in translation units of their own (mg_look_quad.hip: 5 / 6, mg_look_v4.hip:
 // 4, mg_look_hbm.hip: 0); mg_lookahead.hip dispatches.
 //
-// The kernel is step_kernel (mg_stepk.h) with the env-step loop inside: the same workgroup map, the same scene
-// checks, the same LDS view and transfers, the same env_substeps_* calls in the same order -- so an env's state
+// The kernel is built from step_kernel's pieces (mg_stepk.h) with the env-step loop inside: StepForm (what the pair
+// fixes at compile time), xcd_block, carve_view, xfer_state_quad and xfer_state (the LDS view and its transfers), the
+// env_substeps_* calls in step_kernel's order, and launch_env_kernel; the lane map, scene check and quad entry are
+// written out here as there ("One workgroup skeleton", says why) -- so an env's state
 // after h iterations has the bits that h calls of mg_step give it (everything is compiled with -ffp-contract=off,
 // and what the view does not carry from one env-step to the next -- cached shape BBs, the constraints' pre-step
 // products, the robot's targets and motor rates -- is recomputed before use in every env-step, here as there).
-// What differs: the view is loaded once and written back once, S is the sim's scratch pool (never its own state),
+// Its own: the view is loaded once and written back once, S is the sim's scratch pool (never its own state),
 // and there is no episode counter, reward, done flag or reset -- only the outputs of LookOut.
 //
 // TRACE (mg_lookahead_obj, mg_plan_obj, mg_plan_cem_obj; a second instantiation of every pair): the env's view goes
@@ -94,21 +96,16 @@ template <int VAR, int BLK, bool TRACE = false>
 __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_library *__restrict__ L, int task, int max_steps,
                                                        const uint8_t *__restrict__ actions, int H, LookOut out, LookObj obj) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr StepCaps C = step_form_caps(VAR);
-    static_assert(mg_step_blk_ok(VAR, BLK), "not a pair of MG_STEP_FORMS (mg_stepforms.h)");
-    constexpr bool LDS = VAR != 0;
-    constexpr bool COOP = VAR == 4;            // one env per workgroup of 64 lanes
-    constexpr bool QUAD = VAR == 5 || VAR == 6; // QL lanes per env, BLK envs in one 64-lane workgroup
-    constexpr int QL = QUAD ? 64 / BLK : 1;
-    constexpr int NCS = VAR == 4 ? 0 : C.nc;   // compile-time constraint list (0: the env's runtime list)
-    const int lane = COOP ? (int)threadIdx.x : QUAD ? (int)threadIdx.x / QL : BLK == 1 ? 0 : (int)threadIdx.x;
-    const int sub = QUAD ? (int)threadIdx.x % QL : 0;
-    int e = xcd_block(blockIdx.x, gridDim.x) * BLK + (COOP ? 0 : lane);
+    using F = StepForm<VAR, BLK>;
+    constexpr StepCaps C = F::C;
+    const int lane = F::COOP ? (int)threadIdx.x : F::QUAD ? (int)threadIdx.x / F::QL : BLK == 1 ? 0 : (int)threadIdx.x;
+    const int sub = F::QUAD ? (int)threadIdx.x % F::QL : 0;
+    int e = xcd_block(blockIdx.x, gridDim.x) * BLK + (F::COOP ? 0 : lane);
     // QUAD: lanes without an env of their own (past n_envs, or a scene the form cannot hold) take part in the
-    // workgroup barriers as shadows of a valid env and never write HBM: step_kernel's convention, unchanged
+    // workgroup barriers as shadows of a valid env and never write HBM: step_kernel's convention
     bool shadow = false;
     if (e >= S.n_envs) {
-        if (!QUAD) return;
+        if (!F::QUAD) return;
         shadow = true;
         e = S.n_envs - 1;
     }
@@ -127,24 +124,24 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
     [[maybe_unused]] ObjAcc acc;
     if constexpr (TRACE) {
         done_n = max_steps > 0 && n >= 1 && S.episode_steps[e] + n >= max_steps;
-        if (!shadow && (COOP ? lane == 0 : sub == 0)) obj_begin(acc, S, L, e, task);
+        if (!shadow && (F::COOP ? lane == 0 : sub == 0)) obj_begin(acc, S, L, e, task);
     }
     MGProf P;
     MG_PP_INIT(P);
-    if constexpr (LDS) {
+    if constexpr (F::LDS) {
         bool fits = true;
         if (S.nbodies[e] > C.nb || S.nshapes[e] > C.ns || S.ncons[e] > C.nc) {
             if (!shadow && sub == 0) S.overflow[e] |= 16; // scene larger than the variant's LDS caps (never expected)
             fits = false;
         }
-        bool ok = NCS == 0 || (S.ncons[e] == C.nc && S.robot_body0[e] == 0 && S.robot_cons0[e] == 0);
-        for (int c = 0; c < NCS; c++) {
+        bool ok = F::NCS == 0 || (S.ncons[e] == C.nc && S.robot_body0[e] == 0 && S.robot_cons0[e] == 0);
+        for (int c = 0; c < F::NCS; c++) {
             const ConsDesc d = static_cons(c);
             ok = ok && AT(S.ctype, c) == d.type && AT(S.ca, c) == d.a && AT(S.cb, c) == d.b;
         }
-        for (int k = 0; k < S.nshapes[e] && k < C.ns && NCS > 0; k++) ok = ok && shape_body_slot(AT(S.sbody, k)); // arb_body
+        for (int k = 0; k < S.nshapes[e] && k < C.ns && F::NCS > 0; k++) ok = ok && shape_body_slot(AT(S.sbody, k)); // arb_body
         if (!ok && fits && !shadow && sub == 0) S.overflow[e] |= 32; // the compiled constraint list does not describe this scene
-        if (!QUAD && !(fits && ok)) {   // COOP, uniform over the workgroup: nothing is simulated
+        if (!F::QUAD && !(fits && ok)) {   // COOP, uniform over the workgroup: nothing is simulated
             if (lane == 0) {
                 if constexpr (TRACE) obj_emit(acc, S, L, e, task, 0, H, false, out, obj);
                 else look_emit(S, L, e, task, 0, out);
@@ -153,10 +150,10 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
         }
         MGState V = S;
         carve_view(V, smem, C, BLK);
-        if constexpr (QUAD) {
+        if constexpr (F::QUAD) {
             const bool own = !shadow && fits && ok;
             if (!own) n = 0;
-            xfer_state_quad<C.nb, C.ns, C.nc, C.na, QL>(S, V, lane, e, sub, true);
+            xfer_state_quad<C.nb, C.ns, C.nc, C.na, F::QL>(S, V, lane, e, sub);
             if (!fits && sub == 0) { // an empty scene in the env's column: nothing indexes past the caps
                 V.nbodies[lane] = 0; V.nshapes[lane] = 0; V.ncons[lane] = 0; V.nactive[lane] = 0;
             }
@@ -169,7 +166,7 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
                 hw = o > hw ? o : hw;
             }
             for (int h = 0; h < hw; h++) {
-                env_substeps_quad<NCS, QL>(V, L, lane, sub, act[h * astride], P);   // ends with a workgroup barrier
+                env_substeps_quad<F::NCS, F::QL>(V, L, lane, sub, act[h * astride], P);   // ends with a workgroup barrier
                 if constexpr (TRACE) {
                     // Every env-step of the env's own n: its column goes back to scratch from its own lanes, between
                     // that closing barrier and the barrier below (no lane writes the view there: the next env-step
@@ -181,7 +178,7 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
                     // env_substeps_quad.  An env past its n (and a shadow, n = 0) goes on in LDS and touches neither
                     // its scratch column nor its outputs again: both are guarded by own && h < n, and h < n <= H,
                     // e < n_envs bound the trace index (obj_step).
-                    if (own && h < n) xfer_state(S, V, C, lane, e, false, false, sub, QL);
+                    if (own && h < n) xfer_state(S, V, C, lane, e, false, false, sub, F::QL);
                     __threadfence_block();
                     __syncthreads();
                     if (own && sub == 0 && h < n) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);
@@ -189,7 +186,7 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
                     // the env's last step: its column goes back to scratch from its own lanes, between that barrier and
                     // the next env-step's opening one (no lane writes the view there); afterwards the env goes on in LDS
                     // as a shadow does and never writes HBM again
-                    if (own && h + 1 == n) xfer_state(S, V, C, lane, e, false, false, sub, QL);
+                    if (own && h + 1 == n) xfer_state(S, V, C, lane, e, false, false, sub, F::QL);
                 }
             }
             // the env's lane 0 reads scratch rows its sibling lanes wrote back: ordered by the memory model (as
@@ -231,41 +228,12 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
 template <int VAR, int BLK, bool TRACE>
 hipError_t launch_look(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions, int H,
                        const LookOut &out, const LookObj &obj, hipStream_t st) {
-    constexpr size_t lds = VAR == 0 ? 0 : mg_step_lds_bytes(step_form_caps(VAR), BLK);
-    static bool attr_set = false;
-    if (VAR != 0 && !attr_set) {
-        hipError_t err = hipFuncSetAttribute((const void *)lookahead_kernel<VAR, BLK, TRACE>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) {
-            fprintf(stderr, "lookahead form %d/%d: LDS attribute %zu B: %s\n", VAR, BLK, lds, hipGetErrorString(err));
-            return err;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((lookahead_kernel<VAR, BLK, TRACE>), dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 0 ? BLK : 64), lds,
-                       st, S, L, task, max_steps, actions, H, out, obj);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess)
-        fprintf(stderr, "lookahead form %d/%d: launch of %d workgroups, LDS %zu B: %s\n", VAR, BLK,
-                (S.n_envs + BLK - 1) / BLK, lds, hipGetErrorString(err));
-    return err;
-}
-
-template <int VAR, int BLK>
-hipError_t launch_lookahead_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
-                                int H, const LookOut &out, hipStream_t st) {
-    return launch_look<VAR, BLK, false>(S, L, task, max_steps, actions, H, out, LookObj{}, st);
-}
-
-template <int VAR, int BLK>
-hipError_t launch_lookahead_obj_var(const MGState &S, const mg_library *L, int task, int max_steps, const uint8_t *actions,
-                                    int H, const LookOut &out, const LookObj &obj, hipStream_t st) {
-    return launch_look<VAR, BLK, true>(S, L, task, max_steps, actions, H, out, obj, st);
+    return launch_env_kernel<lookahead_kernel<VAR, BLK, TRACE>, VAR, BLK>("lookahead", S, st, L, task, max_steps, actions, H,
+                                                                         out, obj);
 }
 
 // a translation unit instantiates its row of the form table, plain and TRACE: MG_STEP_FORMS_QUAD(MG_LOOK_INSTANTIATE)
-#define MG_LOOK_INSTANTIATE(F, B) \
-    template hipError_t launch_lookahead_var<F, B>(const MGState &, const mg_library *, int, int, const uint8_t *, int, \
-                                                   const LookOut &, hipStream_t); \
-    template hipError_t launch_lookahead_obj_var<F, B>(const MGState &, const mg_library *, int, int, const uint8_t *, \
-                                                       int, const LookOut &, const LookObj &, hipStream_t);
+#define MG_LOOK_INSTANTIATE_ONE(F, B, TRACE) \
+    template hipError_t launch_look<F, B, TRACE>(const MGState &, const mg_library *, int, int, const uint8_t *, int, \
+                                                 const LookOut &, const LookObj &, hipStream_t);
+#define MG_LOOK_INSTANTIATE(F, B) MG_LOOK_INSTANTIATE_ONE(F, B, false) MG_LOOK_INSTANTIATE_ONE(F, B, true)

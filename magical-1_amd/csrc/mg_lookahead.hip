@@ -10,18 +10,11 @@ static_assert(LOOK_OBJ_FINAL == MG_OBJ_FINAL && LOOK_OBJ_RETURN == MG_OBJ_RETURN
               "mg_launch.h restates the header's objective kinds");
 
 hipError_t mg_launch_lookahead(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
-                               const uint8_t *actions, int H, const LookOut &out, hipStream_t st) {
+                               const uint8_t *actions, int H, const LookOut &out, const LookObj *obj, hipStream_t st) {
 #define MG_LOOK_CASE(F, B) \
-    if (form == F && blk == B) return launch_lookahead_var<F, B>(S, L, task, max_steps, actions, H, out, st);
-    MG_STEP_FORMS(MG_LOOK_CASE)
-#undef MG_LOOK_CASE
-    return hipErrorInvalidValue;
-}
-
-hipError_t mg_launch_lookahead_obj(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
-                                   const uint8_t *actions, int H, const LookOut &out, const LookObj &obj, hipStream_t st) {
-#define MG_LOOK_CASE(F, B) \
-    if (form == F && blk == B) return launch_lookahead_obj_var<F, B>(S, L, task, max_steps, actions, H, out, obj, st);
+    if (form == F && blk == B) \
+        return obj ? launch_look<F, B, true>(S, L, task, max_steps, actions, H, out, *obj, st) \
+                   : launch_look<F, B, false>(S, L, task, max_steps, actions, H, out, LookObj{}, st);
     MG_STEP_FORMS(MG_LOOK_CASE)
 #undef MG_LOOK_CASE
     return hipErrorInvalidValue;
@@ -62,7 +55,7 @@ static int lookahead_run(mg_sim *s, const char *fn, const uint8_t *actions, int3
     const LookOut lo = {out->score, out->steps, out->bodies, out->counts, out->errors};
     const bool wanted = oo && (oo->value || oo->peak || oo->peak_step || oo->score_trace || oo->reward_trace);
     if (!obj || (obj->kind == MG_OBJ_FINAL && !wanted)) {
-        HIPC(mg_launch_lookahead(R.P.S, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+        HIPC(mg_launch_lookahead(R.P.S, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, nullptr, st));
         return 0;
     }
     LookObj a = objective_args(s, obj);
@@ -70,7 +63,7 @@ static int lookahead_run(mg_sim *s, const char *fn, const uint8_t *actions, int3
         a.value = oo->value; a.peak = oo->peak; a.peak_step = oo->peak_step;
         a.score_trace = oo->score_trace; a.reward_trace = oo->reward_trace;
     }
-    HIPC(mg_launch_lookahead_obj(R.P.S, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, a, st));
+    HIPC(mg_launch_lookahead(R.P.S, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, &a, st));
     return 0;
 }
 

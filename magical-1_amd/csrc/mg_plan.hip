@@ -175,14 +175,14 @@ int plan_rollouts(mg_sim *s, const MGState &F, const uint8_t *actions, int H, co
                   int32_t *steps, int32_t *errors, hipStream_t st) {
     if (!obj || obj->kind == MG_OBJ_FINAL) {
         const LookOut lo = {scores, steps, nullptr, nullptr, errors};
-        HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, st));
+        HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, nullptr, st));
         return 0;
     }
     // the traced kernel with `value` pointed at the [K][N] scores and no s_n output
     const LookOut lo = {nullptr, steps, nullptr, nullptr, errors};
     LookObj a = objective_args(s, obj);
     a.value = scores;
-    HIPC(mg_launch_lookahead_obj(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, a, st));
+    HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, &a, st));
     return 0;
 }
 

@@ -62,7 +62,7 @@ __device__ __forceinline__ void xfer_state(const MGState &S, const MGState &V, c
 #pragma unroll 1
     for (int r = r0; r < c.na; r += rs) { // arbiter slots: only live ones carry data
         XS(akey, r);
-        const int key = in ? V.akey[(uint32_t)r * blk + lane] : V.akey[(uint32_t)r * blk + lane];
+        const int key = V.akey[(uint32_t)r * blk + lane];   // in: just loaded
         if (key < 0) continue;
         XS(anx, r); XS(any, r); XS(au, r); XS(astamp, r); XS(astate, r); XS(acount, r); XS(asa, r); XS(asb, r);
 #pragma unroll 1
@@ -91,45 +91,40 @@ __device__ __forceinline__ void xfer_state(const MGState &S, const MGState &V, c
 #undef XF
 }
 
-// HBM <-> LDS view transfer of what the substeps read (in) / what later env-steps need (out): bodies (incl. bias
-// velocities and the rotation cache), the constraints' parameters and warm-start impulses, the live arbiters
-// (key, contacts, warm-start hashes) and the active list; cached shape BBs and the constraints' pre-step products
-// are recomputed before use.  Rows sub, sub + QL, ... of every [row][N] HBM array <-> the [row][BLK] LDS array's
-// column `lane`.  The slot caps are compile-time, so every loop has a constant trip count and no branch (rows
-// past the cap repeat the last row: the same value loaded and stored twice) and each array's loads are in
-// flight together instead of one HBM round trip per row (round 5: the `in` transfer was ~15% of the robot
-// scenes' step kernel as a chain of dependent HBM latencies).  Live arbiters' contact rows likewise in one
-// block per slot.
+// The quad forms' HBM -> LDS view load of what the substeps read: bodies (incl. bias velocities and the rotation
+// cache), the constraints' parameters and warm-start impulses, the live arbiters (key, contacts, warm-start hashes)
+// and the active list; cached shape BBs and the constraints' pre-step products are recomputed before use.  Rows sub,
+// sub + QL, ... of every [row][N] HBM array -> the [row][BLK] LDS array's column `lane`.  The slot caps are
+// compile-time, so every loop has a constant trip count and no branch (rows past the cap repeat the last row: the
+// same value loaded twice) and each array's loads are in flight together instead of one HBM round trip per row
+// (round 5: this transfer was ~15% of the robot scenes' step kernel as a chain of dependent HBM latencies).  Live
+// arbiters' contact rows likewise in one block per slot.  Loads only: the quad forms write back through xfer_state
+// (rows sub, sub + QL, ...), because stores have no latency chain to batch.
 template <int ROWS, int QL, typename T>
-MG_DEV void xq(T *lds, T *hbm, int blk, int lane, int N, int e, int sub, bool in, int lrow0 = 0, int hrow0 = 0) {
+MG_DEV void xq(T *lds, const T *hbm, int blk, int lane, int N, int e, int sub, int lrow0 = 0, int hrow0 = 0) {
 #pragma unroll
     for (int k = 0; k < (ROWS + QL - 1) / QL; k++) {
         const int r = sub + k * QL < ROWS ? sub + k * QL : ROWS - 1;
-        const uint32_t li = (uint32_t)(lrow0 + r) * blk + lane, hi = (uint32_t)(hrow0 + r) * N + e;
-        if (in) lds[li] = hbm[hi]; else hbm[hi] = lds[li];
+        lds[(uint32_t)(lrow0 + r) * blk + lane] = hbm[(uint32_t)(hrow0 + r) * N + e];
     }
 }
 
 template <int NB, int NS, int NC, int NA, int QL>
-__device__ __forceinline__ void xfer_state_quad(const MGState &S, const MGState &V, int lane, int e, int sub, bool in) {
+__device__ __forceinline__ void xfer_state_quad(const MGState &S, const MGState &V, int lane, int e, int sub) {
     const int blk = V.N, N = S.N;
     // groups of a few arrays are scheduled on their own (sched_barrier): their loads are in flight together,
     // but the whole transfer is not hoisted into one block (that held ~200 VGPRs of loaded values and made
     // the kernel spill)
-#define XQ(f, rows) xq<rows, QL>(V.f, S.f, blk, lane, N, e, sub, in)
+#define XQ(f, rows) xq<rows, QL>(V.f, S.f, blk, lane, N, e, sub)
 #define XQ_GROUP() __builtin_amdgcn_sched_barrier(0)
     XQ(bpx, NB); XQ(bpy, NB); XQ(bvx, NB); XQ(bvy, NB); XQ_GROUP();
     XQ(ba, NB); XQ(bw, NB); XQ(bvbx, NB); XQ(bvby, NB); XQ_GROUP();
     XQ(bwb, NB); XQ(brc, NB); XQ(brs, NB); XQ(bacache, NB); XQ_GROUP();
-    if (in) {   // constraint parameter slots MAXF, MAXB, BCOEF, JACC, JACC2 and the type parameters 8-11
+    // constraint parameter slots MAXF, MAXB, BCOEF, JACC, JACC2 and the type parameters 8-11
 #pragma unroll
-        for (int k = 0; k < CP_NUM; k++) {
-            if (k <= CP_JACC2 || (k >= 8 && k <= 11)) xq<NC, QL>(V.cp, S.cp, blk, lane, N, e, sub, true, k * NC, k * MG_MAX_CONS);
-            if (k == 2 || k == 8 || k == 11) XQ_GROUP();
-        }
-    } else {    // the warm-start impulses
-        xq<NC, QL>(V.cp, S.cp, blk, lane, N, e, sub, false, CP_JACC * NC, CP_JACC * MG_MAX_CONS);
-        xq<NC, QL>(V.cp, S.cp, blk, lane, N, e, sub, false, CP_JACC2 * NC, CP_JACC2 * MG_MAX_CONS);
+    for (int k = 0; k < CP_NUM; k++) {
+        if (k <= CP_JACC2 || (k >= 8 && k <= 11)) xq<NC, QL>(V.cp, S.cp, blk, lane, N, e, sub, k * NC, k * MG_MAX_CONS);
+        if (k == 2 || k == 8 || k == 11) XQ_GROUP();
     }
     XQ_GROUP();
     XQ(akey, NA);   // arbiter slots: only live ones carry data
@@ -137,47 +132,35 @@ __device__ __forceinline__ void xfer_state_quad(const MGState &S, const MGState 
     for (int k = 0; k < (NA + QL - 1) / QL; k++) {
         const int r = sub + k * QL;
         if (r >= NA || V.akey[(uint32_t)r * blk + lane] < 0) continue;
-#define XA(f) do { if (in) V.f[(uint32_t)r * blk + lane] = S.f[(uint32_t)r * N + e]; \
-                   else S.f[(uint32_t)r * N + e] = V.f[(uint32_t)r * blk + lane]; } while (0)
+#define XA(f) V.f[(uint32_t)r * blk + lane] = S.f[(uint32_t)r * N + e]
         XA(anx); XA(any); XA(au); XA(astamp); XA(astate); XA(acount); XA(asa); XA(asb);
-#pragma unroll
-        for (int f = 0; f < 2 * AC_NUM; f++) {
-            if (in) V.acon[(uint32_t)(f * NA + r) * blk + lane] = S.acon[(uint32_t)(f * MG_MAX_ARB + r) * N + e];
-            else S.acon[(uint32_t)(f * MG_MAX_ARB + r) * N + e] = V.acon[(uint32_t)(f * NA + r) * blk + lane];
-        }
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            if (in) V.ahash[(uint32_t)(h * NA + r) * blk + lane] = S.ahash[(uint32_t)(h * MG_MAX_ARB + r) * N + e];
-            else S.ahash[(uint32_t)(h * MG_MAX_ARB + r) * N + e] = V.ahash[(uint32_t)(h * NA + r) * blk + lane];
-        }
 #undef XA
+#pragma unroll
+        for (int f = 0; f < 2 * AC_NUM; f++)
+            V.acon[(uint32_t)(f * NA + r) * blk + lane] = S.acon[(uint32_t)(f * MG_MAX_ARB + r) * N + e];
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+            V.ahash[(uint32_t)(h * NA + r) * blk + lane] = S.ahash[(uint32_t)(h * MG_MAX_ARB + r) * N + e];
     }
-    if (sub == 0) {
-        if (in) V.nactive[lane] = S.nactive[e]; else S.nactive[e] = V.nactive[lane];
-    }
-    // the active list: its length is read back from this lane's own copy (sub-lane 0 wrote it just above for
-    // `in`; the solver lane wrote it before the closing barrier for `out`) -- rows past it are dead
-    const int nact = in ? S.nactive[e] : V.nactive[lane];
+    if (sub == 0) V.nactive[lane] = S.nactive[e];
+    // the active list: every lane reads its length from HBM (sub-lane 0's copy just above is not yet published to
+    // its siblings) -- rows past it are dead
+    const int nact = S.nactive[e];
 #pragma unroll
     for (int k = 0; k < (NA + QL - 1) / QL; k++) {
         const int r = sub + k * QL;
-        if (r < nact) {
-            if (in) V.active[(uint32_t)r * blk + lane] = S.active[(uint32_t)r * N + e];
-            else S.active[(uint32_t)r * N + e] = V.active[(uint32_t)r * blk + lane];
-        }
+        if (r < nact) V.active[(uint32_t)r * blk + lane] = S.active[(uint32_t)r * N + e];
     }
     if (sub == 0) {
-#define XS1(f) do { if (in) V.f[lane] = S.f[e]; else S.f[e] = V.f[lane]; } while (0)
-        XS1(curr_dt); XS1(stamp); XS1(overflow);
-        if (in) { XS1(target_speed); XS1(rel_turn); XS1(target_finger); XS1(nbodies); XS1(nshapes); XS1(ncons);
-                  XS1(robot_body0); XS1(robot_cons0); }
+#define XS1(f) V.f[lane] = S.f[e]
+        XS1(curr_dt); XS1(stamp); XS1(overflow); XS1(target_speed); XS1(rel_turn); XS1(target_finger); XS1(nbodies);
+        XS1(nshapes); XS1(ncons); XS1(robot_body0); XS1(robot_cons0);
 #undef XS1
     }
-    if (in) {   // read-only during the substeps
-        XQ(bminv, NB); XQ(biinv, NB); XQ(sr, NS); XQ(su, NS); XQ_GROUP();
-        XQ(sgroup, NS); XQ(shash, NS); XQ(sbody, NS); XQ(spoly, NS);
-        XQ_GROUP();
-    }
+    // read-only during the substeps
+    XQ(bminv, NB); XQ(biinv, NB); XQ(sr, NS); XQ(su, NS); XQ_GROUP();
+    XQ(sgroup, NS); XQ(shash, NS); XQ(sbody, NS); XQ(spoly, NS);
+    XQ_GROUP();
 #undef XQ_GROUP
 #undef XQ
 }
@@ -218,67 +201,76 @@ __device__ __forceinline__ void env_substeps_coop(const MGState &V, const mg_lib
     }
 }
 
+// What a (form, envs per workgroup) pair fixes at compile time, for step_kernel and lookahead_kernel (mg_lookahead.h)
+// alike.  (The lane map, scene check and quad entry that follow it in both kernels are still written out in each:
+// moved into shared functions, the quad kernels' register figures changed -- DESIGN.md, "One workgroup skeleton".)
+template <int VAR, int BLK>
+struct StepForm {
+    static_assert(mg_step_blk_ok(VAR, BLK), "not a pair of MG_STEP_FORMS (mg_stepforms.h)");
+    static constexpr StepCaps C = step_form_caps(VAR);
+    static constexpr bool LDS = VAR != 0;
+    static constexpr bool COOP = VAR == 4;             // one env per workgroup of 64 lanes
+    static constexpr bool QUAD = VAR == 5 || VAR == 6; // QL lanes per env, BLK envs in one 64-lane workgroup
+    static constexpr int QL = QUAD ? 64 / BLK : 1;
+    static constexpr int NCS = VAR == 4 ? 0 : C.nc;    // compile-time constraint list (0: the env's runtime list)
+};
+
 template <int VAR, int BLK>
 __global__ void __launch_bounds__(64) step_kernel(MGState S, const mg_library *__restrict__ L, TaskCfg cfg, int max_steps,
                                                   int auto_reset, const uint8_t *__restrict__ actions, float *reward,
                                                   uint8_t *done, double *eval_score, uint8_t *reset_mask) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr StepCaps C = step_form_caps(VAR);
-    static_assert(mg_step_blk_ok(VAR, BLK), "not a pair of MG_STEP_FORMS (mg_stepforms.h)");
-    constexpr bool LDS = VAR != 0;
-    constexpr bool COOP = VAR == 4;            // one env per workgroup of 64 lanes
-    constexpr bool QUAD = VAR == 5 || VAR == 6; // QL lanes per env, BLK envs in one 64-lane workgroup
-    constexpr int QL = QUAD ? 64 / BLK : 1;
-    constexpr int NCS = VAR == 4 ? 0 : C.nc;   // compile-time constraint list (0: the env's runtime list)
-    const int lane = COOP ? (int)threadIdx.x : QUAD ? (int)threadIdx.x / QL : BLK == 1 ? 0 : (int)threadIdx.x;
-    const int sub = QUAD ? (int)threadIdx.x % QL : 0;
-    int e = xcd_block(blockIdx.x, gridDim.x) * BLK + (COOP ? 0 : lane);
+    using F = StepForm<VAR, BLK>;
+    constexpr StepCaps C = F::C;
+    const int lane = F::COOP ? (int)threadIdx.x : F::QUAD ? (int)threadIdx.x / F::QL : BLK == 1 ? 0 : (int)threadIdx.x;
+    const int sub = F::QUAD ? (int)threadIdx.x % F::QL : 0;
+    int e = xcd_block(blockIdx.x, gridDim.x) * BLK + (F::COOP ? 0 : lane);
     // QUAD: lanes without an env of their own (past n_envs, or a scene the form cannot hold) still take
     // part in the workgroup barriers as shadows of a valid env; they never write HBM
     bool shadow = false;
     if (e >= S.n_envs) {
-        if (!QUAD) return;
+        if (!F::QUAD) return;
         shadow = true;
         e = S.n_envs - 1;
     }
     const int a = actions[e];
     MGProf P;
     MG_PP_INIT(P);
-    if constexpr (LDS) {
+    if constexpr (F::LDS) {
         bool fits = true;
         if (S.nbodies[e] > C.nb || S.nshapes[e] > C.ns || S.ncons[e] > C.nc) {
             if (!shadow && sub == 0) {
                 S.overflow[e] |= 16; // scene larger than the variant's LDS caps (never expected)
                 if (reset_mask) reset_mask[e] = 0;
             }
-            if (!QUAD) return;
+            if (!F::QUAD) return;
             fits = false;
         }
-        bool ok = NCS == 0 || (S.ncons[e] == C.nc && S.robot_body0[e] == 0 && S.robot_cons0[e] == 0);
-        for (int c = 0; c < NCS; c++) {
+        bool ok = F::NCS == 0 || (S.ncons[e] == C.nc && S.robot_body0[e] == 0 && S.robot_cons0[e] == 0);
+        for (int c = 0; c < F::NCS; c++) {
             const ConsDesc d = static_cons(c);
             ok = ok && AT(S.ctype, c) == d.type && AT(S.ca, c) == d.a && AT(S.cb, c) == d.b;
         }
-        for (int k = 0; k < S.nshapes[e] && k < C.ns && NCS > 0; k++) ok = ok && shape_body_slot(AT(S.sbody, k)); // arb_body
+        for (int k = 0; k < S.nshapes[e] && k < C.ns && F::NCS > 0; k++) ok = ok && shape_body_slot(AT(S.sbody, k)); // arb_body
         if (!ok && fits) { // the compiled constraint list does not describe this scene (never expected)
             if (!shadow && sub == 0) {
                 S.overflow[e] |= 32;
                 if (reset_mask) reset_mask[e] = 0;
             }
-            if (!QUAD) return;
+            if (!F::QUAD) return;
         }
         // the view is built from the LDS carve only (never merged with the HBM pointers), so every
         // access through it compiles to ds_* with a constant offset from the lane's column
         MGState V = S;
         carve_view(V, smem, C, BLK);
-        if constexpr (QUAD) {
+        if constexpr (F::QUAD) {
             const bool own = !shadow && fits && ok;
-            xfer_state_quad<C.nb, C.ns, C.nc, C.na, QL>(S, V, lane, e, sub, true);
+            xfer_state_quad<C.nb, C.ns, C.nc, C.na, F::QL>(S, V, lane, e, sub);
             if (!fits && sub == 0) { // an empty scene in the env's column: nothing indexes past the caps
                 V.nbodies[lane] = 0; V.nshapes[lane] = 0; V.ncons[lane] = 0; V.nactive[lane] = 0;
             }
-            env_substeps_quad<NCS, QL>(V, L, lane, sub, a, P);
-            if (own) xfer_state(S, V, C, lane, e, false, false, sub, QL);   // stores: no latency chain to batch
+            env_substeps_quad<F::NCS, F::QL>(V, L, lane, sub, a, P);
+            if (own) xfer_state(S, V, C, lane, e, false, false, sub, F::QL);   // stores: no latency chain to batch
             // the env's lane 0 scores from HBM rows its sibling lanes just wrote back: order them
             // by the memory model, not by one wavefront's in-order memory pipe
             __threadfence_block();
@@ -305,7 +297,7 @@ __global__ void __launch_bounds__(64) step_kernel(MGState S, const mg_library *_
     // VecEnv auto-reset (next obs = first frame of the new episode) runs as reset_kernel on this mask -- or,
     // for the robot scenes without layout randomisation, here: their reset is serial straight-line code (no
     // rejection sampling), so the env's own lane runs it and the step saves a launch (cfg.fused_reset)
-    if constexpr (VAR == 5 || VAR == 6) {
+    if constexpr (F::QUAD) {
         if (cfg.fused_reset && d && auto_reset) {
             TaskCfg rc = cfg;
             rc.coop = 0;
@@ -317,28 +309,34 @@ __global__ void __launch_bounds__(64) step_kernel(MGState S, const mg_library *_
     MG_PP_END(P, (threadIdx.x & 63) == 0, 32);
 }
 
-template <int VAR, int BLK>
-hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, int max_steps, int auto_reset,
-                                  const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
-                                  uint8_t *reset_mask, hipStream_t st) {
+// The launch of a compiled pair's kernel (`what` names it in the messages): one workgroup per BLK envs, the view's
+// bytes of dynamic LDS, asked for once per kernel (the flag is per instantiation, and Kernel is a parameter)
+template <auto Kernel, int VAR, int BLK, class... A>
+hipError_t launch_env_kernel(const char *what, const MGState &S, hipStream_t st, A... args) {
     constexpr size_t lds = VAR == 0 ? 0 : mg_step_lds_bytes(step_form_caps(VAR), BLK);
     static bool attr_set = false;
     if (VAR != 0 && !attr_set) {
-        hipError_t err = hipFuncSetAttribute((const void *)step_kernel<VAR, BLK>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t err = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) {
-            fprintf(stderr, "step form %d/%d: LDS attribute %zu B: %s\n", VAR, BLK, lds, hipGetErrorString(err));
+            fprintf(stderr, "%s form %d/%d: LDS attribute %zu B: %s\n", what, VAR, BLK, lds, hipGetErrorString(err));
             return err;
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL((step_kernel<VAR, BLK>), dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 0 ? BLK : 64), lds, st, S, L, cfg,
-                       max_steps, auto_reset, actions, reward, done, eval_score, reset_mask);
+    hipLaunchKernelGGL(Kernel, dim3((S.n_envs + BLK - 1) / BLK), dim3(VAR == 0 ? BLK : 64), lds, st, S, args...);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
-        fprintf(stderr, "step form %d/%d: launch of %d workgroups, LDS %zu B: %s\n", VAR, BLK,
+        fprintf(stderr, "%s form %d/%d: launch of %d workgroups, LDS %zu B: %s\n", what, VAR, BLK,
                 (S.n_envs + BLK - 1) / BLK, lds, hipGetErrorString(err));
     return err;
+}
+
+template <int VAR, int BLK>
+hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, int max_steps, int auto_reset,
+                           const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
+                           uint8_t *reset_mask, hipStream_t st) {
+    return launch_env_kernel<step_kernel<VAR, BLK>, VAR, BLK>("step", S, st, L, cfg, max_steps, auto_reset, actions, reward,
+                                                              done, eval_score, reset_mask);
 }
 
 // a translation unit instantiates its row of the form table: MG_STEP_FORMS_QUAD(MG_STEP_INSTANTIATE)
