@@ -360,6 +360,43 @@ int mg_plan_obj(mg_sim *sim, const uint8_t *actions_dev, int32_t H, int32_t K, c
 int mg_plan_cem_obj(mg_sim *sim, uint8_t *actions_dev, uint16_t *weights_dev, int32_t warm,
                     int32_t H, int32_t K, int32_t iters, int32_t elites, int32_t alpha, int32_t repeat,
                     uint64_t key, uint64_t step, const mg_objective *objective, const mg_plan_cem_out *out, void *stream);
+/* Beam search over action segments: mg_plan that prunes while it rolls out.  The horizon is cut into D = ceil(H / seg)
+ * segments, segment d the steps [d*seg, min(H, (d+1)*seg)).  Every slot k of env e starts from the env's current state
+ * (mg_plan's fan-out).  In segment d slot k applies actions[h][k][e], for the segment's h, to whatever lineage occupies
+ * the slot, and plans[h][k][e] = actions[h][k][e].  After every segment but the last the env's slots are resampled:
+ * the `survivors` slots with the highest value survive, the lower k first among equal values (mg_plan_cem's elite
+ * rule), and stay where they are; with the survivors in increasing k s_0 < s_1 < .. and the losers l_0 < l_1 < ..,
+ * loser l_j becomes a copy of s_(j mod survivors): its whole state with the error flags, the objective's accumulators
+ * and plans[0 .. segment end).  The copy is made in place in the fan pool, on the device.
+ * After each segment the value of slot k is bit for bit what mg_lookahead_obj (mg_lookahead for FINAL) returns for the
+ * action prefix of the slot's lineage -- plans[0 .. segment end)[k][e] -- from the env's current state: the same
+ * per-env horizon, stop at the terminal step, steps and error flags.  On return column (k, e) of plans_dev is the full
+ * action sequence of the lineage that ends in slot k, and mg_plan / mg_plan_obj on plans_dev reproduces values, steps
+ * and errors.  survivors == K or seg >= H gives mg_plan / mg_plan_obj on actions_dev in every output, plans == actions
+ * and parents[d][k] = k.  Caller-owned device outputs (N = num_envs): */
+typedef struct {
+    int32_t *best;         /* i32[N]: slot k of the env's best lineage after the last segment (highest value, lowest k
+                              on ties); required */
+    double  *best_value;   /* f64[N]; NULL ok */
+    uint8_t *first_action; /* u8[N] = plans[0][best[e]][e]; NULL ok */
+    uint8_t *best_plan;    /* u8[H][N] = plans[:, best[e], e]; NULL ok */
+    double  *values;       /* f64[K][N] after the last segment; NULL ok */
+    int32_t *steps;        /* i32[K][N] total env-steps of the lineage; NULL ok */
+    int32_t *errors;       /* i32[K][N] as mg_plan_out.errors, of the lineage; NULL ok */
+    double  *depth_values; /* f64[D][K][N]: slot k's value after segment d, BEFORE the resample; NULL ok */
+    int32_t *parents;      /* i32[D-1][K][N]: parent slot chosen at boundary d (k itself for a survivor); NULL ok;
+                              unread when D == 1 */
+} mg_plan_beam_out;
+/* actions_dev: device u8[H][K][N], mg_plan's layout, read only.  plans_dev: device u8[H][K][N], caller-owned output.
+ * 1 <= H <= 4096, K and K * N as for mg_plan, 1 <= seg <= H, 1 <= survivors <= K.  objective NULL = FINAL.
+ * The sim is observationally untouched, exactly as stated for mg_plan.  The rollouts run on mg_plan's fan pool, which
+ * also holds what the segments pass between them; the pool is (re)allocated as in mg_plan (those calls alone
+ * synchronise the device).  Everything else, every segment and resample included, is enqueued on `stream` with no host
+ * sync.
+ * Returns -22 and launches nothing for a null sim / actions_dev / plans_dev / out / out->best, any argument outside the
+ * ranges above, or an objective that mg_plan_obj refuses. */
+int mg_plan_beam(mg_sim *sim, const uint8_t *actions_dev, uint8_t *plans_dev, int32_t H, int32_t K, int32_t seg,
+                 int32_t survivors, const mg_objective *objective, const mg_plan_beam_out *out, void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

@@ -61,12 +61,22 @@ struct LookOut { double *score; int32_t *steps; double *bodies; int32_t *counts;
 // device pointers of mg_objective_out, all of which may be null -- and here LookOut.score may be null too (a plan's
 // [K][N] buffer receives `value` instead).  debug: the sim pays the dense debug reward (MG_DEBUG_REWARD).
 enum { LOOK_OBJ_FINAL = 0, LOOK_OBJ_RETURN = 1, LOOK_OBJ_PEAK = 2 };   // = MG_OBJ_* (checked in mg_lookahead.hip)
+// mg_plan_beam: an objective continued over several launches on one pool.  Per-rollout arrays [n_envs] that hold,
+// between two launches, G before the tail term, P, g_k and kp of the env-steps done so far, their number k, and whether
+// one of them ended the episode.  G null: no carry (every other call).  load 0: the launch starts the objective as
+// always and only stores the carry; 1: it takes it up from the carry.  It stores the carry in either case
+struct LookCarry {
+    double *G, *P, *g;
+    int32_t *kp, *k, *ended;
+    int load;
+};
 struct LookObj {
     int kind, debug;
     double gamma, tail;
     double *value, *peak;
     int32_t *peak_step;
     double *score_trace, *reward_trace;   // f64[H][n_envs], step-major as the actions
+    LookCarry carry;
 };
 // one compiled lookahead kernel: a pair as above, plain (obj is not read) or TRACE
 template <int VAR, int BLK, bool TRACE>

@@ -17,7 +17,9 @@
 // back to its scratch column after EVERY env-step, as mg_step's does, and the env's scoring lane evaluates the task's
 // score s_k and mg_step's reward r_k there with score_env / debug_reward as they are -- the bits of mg_step's scoring
 // by construction -- and accumulates the objective (LookObj, mg_launch.h; the definitions: include/magical_sim.h and
-// DESIGN.md).  Everything TRACE adds is under `if constexpr (TRACE)`.
+// DESIGN.md).  mg_plan_beam continues an objective over several launches on one pool through LookObj.carry: the
+// accumulators are stored per rollout on exit and, when the carry says so, loaded on entry in place of obj_begin.
+// Everything TRACE adds is under `if constexpr (TRACE)`.
 #pragma once
 #include "mg_stepk.h"
 
@@ -49,12 +51,23 @@ MG_DEV void look_emit(const MGState &S, const mg_library *L, int e, int task, in
 struct ObjAcc {
     double G, P, g, s;   // the return so far, the peak so far, g_k, s_k (k: env-steps done)
     int kp;
+    int k0;              // env-steps done in earlier launches (LookCarry; 0 without one): kp counts from the first launch
+    bool ended;          // one of those steps ended the episode
 };
 
 // x_0: the scratch column as the fan-out copy left it (called before the env's first write-back)
 MG_DEV void obj_begin(ObjAcc &a, const MGState &S, const mg_library *L, int e, int task) {
     a.s = score_env(S, L, e, task);
     a.G = 0.0; a.P = a.s; a.g = 1.0; a.kp = 0;
+    a.k0 = 0; a.ended = false;
+}
+
+// the same with a carry (o.carry.G not null, e < n_envs) that says load: the accumulators as the earlier launches left
+// them; s_k is scored from the scratch column, which holds x_k -- the bits the earlier launch's last obj_step got
+MG_DEV void obj_resume(ObjAcc &a, const MGState &S, const mg_library *L, int e, int task, const LookCarry &c) {
+    a.s = score_env(S, L, e, task);
+    a.G = c.G[e]; a.P = c.P[e]; a.g = c.g[e]; a.kp = c.kp[e];
+    a.k0 = c.k[e]; a.ended = c.ended[e] != 0;
 }
 
 // after env-step k = h + 1, with x_k in the scratch column (h < n <= H and e < n_envs: the trace index h * n_envs + e
@@ -65,7 +78,7 @@ MG_DEV void obj_step(ObjAcc &a, const MGState &S, const mg_library *L, int e, in
     a.G = a.G + a.g * r;
     a.g = a.g * o.gamma;
     const double v = a.g * s;
-    if (v > a.P) { a.P = v; a.kp = h + 1; }
+    if (v > a.P) { a.P = v; a.kp = a.k0 + h + 1; }
     a.s = s;
     const size_t i = (size_t)h * (size_t)S.n_envs + (size_t)e;
     if (o.score_trace) o.score_trace[i] = s;
@@ -79,7 +92,13 @@ MG_DEV void obj_emit(const ObjAcc &a, const MGState &S, const mg_library *L, int
     if (out.score) out.score[e] = a.s;
     look_emit<false>(S, L, e, task, n, out);
     double G = a.G;
-    if (!(n >= 1 && done_n)) G = G + (a.g * o.tail) * a.s;   // the episode goes on past the horizon: its tail value
+    const bool ends = n >= 1 && done_n;
+    if (o.carry.G) {   // (before the tail term: the next launch adds to the sum itself)
+        const LookCarry &c = o.carry;
+        c.G[e] = a.G; c.P[e] = a.P; c.g[e] = a.g; c.kp[e] = a.kp;
+        c.k[e] = a.k0 + n; c.ended[e] = (a.ended || ends) ? 1 : 0;
+    }
+    if (!ends && !a.ended) G = G + (a.g * o.tail) * a.s;   // the episode goes on past the horizon: its tail value
     if (o.value) o.value[e] = o.kind == LOOK_OBJ_RETURN ? G : o.kind == LOOK_OBJ_PEAK ? a.P : a.s;
     if (o.peak) o.peak[e] = a.P;
     if (o.peak_step) o.peak_step[e] = a.kp;
@@ -124,7 +143,10 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
     [[maybe_unused]] ObjAcc acc;
     if constexpr (TRACE) {
         done_n = max_steps > 0 && n >= 1 && S.episode_steps[e] + n >= max_steps;
-        if (!shadow && (F::COOP ? lane == 0 : sub == 0)) obj_begin(acc, S, L, e, task);
+        if (!shadow && (F::COOP ? lane == 0 : sub == 0)) {
+            if (obj.carry.G && obj.carry.load) obj_resume(acc, S, L, e, task, obj.carry);
+            else obj_begin(acc, S, L, e, task);
+        }
     }
     MGProf P;
     MG_PP_INIT(P);

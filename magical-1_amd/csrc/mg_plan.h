@@ -17,7 +17,10 @@ struct PlanRow { uint64_t src, dst; uint32_t esize, pad; };
 
 // One allocation (P.mem) holds the state rows, the rollouts' scores (f64[P.S.N]: the reduction's input also when the
 // caller wants no scores), the device table of the fan-out's rows (the rollout rows of the sim's pool zipped with this
-// pool's) and mg_plan_cem's per-env scratch, the elite threshold (cem_thr f64[num_envs], cem_kthr i32[num_envs])
+// pool's), mg_plan_cem's per-env scratch, the elite threshold (cem_thr f64[num_envs], cem_kthr i32[num_envs]), and
+// mg_plan_beam's per-rollout scratch (mg_beam.h), every array [P.S.N]: the objective's carry (LookCarry's arrays), a
+// segment's env-steps, the survivor list and the parent slots, and the table of the rows a resample clones -- this
+// pool's rollout rows on both sides, then the carry's six
 struct RolloutPool {
     StatePool P;
     PlanRow *rows = nullptr;
@@ -26,6 +29,11 @@ struct RolloutPool {
     double *scores = nullptr;
     double *cem_thr = nullptr;
     int32_t *cem_kthr = nullptr;
+    double *beam_G = nullptr, *beam_P = nullptr, *beam_g = nullptr;
+    int32_t *beam_kp = nullptr, *beam_k = nullptr, *beam_ended = nullptr;
+    int32_t *beam_steps = nullptr, *beam_surv = nullptr, *beam_parent = nullptr;
+    PlanRow *beam_rows = nullptr;
+    int beam_nrows = 0;   // with the carry's rows, which come last (a FINAL resample clones beam_nrows - 6)
 };
 
 // dst column k * n_envs + e <- src column e, for every row, k < K and e < n_envs

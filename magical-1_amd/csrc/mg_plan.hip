@@ -152,6 +152,11 @@ int rollout_reserve(mg_sim *s, RolloutPool &R, int M, const char *fn) {
         T.rows = c.take<PlanRow>(src.size());
         T.cem_thr = c.take<double>((size_t)s->main.S.n_envs);
         T.cem_kthr = c.take<int32_t>((size_t)s->main.S.n_envs);
+        const size_t N = (size_t)T.P.S.N;
+        T.beam_G = c.take<double>(N); T.beam_P = c.take<double>(N); T.beam_g = c.take<double>(N);
+        T.beam_kp = c.take<int32_t>(N); T.beam_k = c.take<int32_t>(N); T.beam_ended = c.take<int32_t>(N);
+        T.beam_steps = c.take<int32_t>(N); T.beam_surv = c.take<int32_t>(N); T.beam_parent = c.take<int32_t>(N);
+        T.beam_rows = c.take<PlanRow>(src.size() + 6);
     });
     if (err != hipSuccess)
         return set_err(-12, std::string(fn) + ": rollout pool for " + std::to_string(M) + " rollouts: " + hipGetErrorString(err));
@@ -161,6 +166,18 @@ int rollout_reserve(mg_sim *s, RolloutPool &R, int M, const char *fn) {
     std::vector<PlanRow> pr;
     for (size_t i = 0; i < src.size(); i++) pr.push_back(PlanRow{src[i].off, dst[i].off, src[i].esize, 0u});
     err = hipMemcpy(T.rows, pr.data(), pr.size() * sizeof(PlanRow), hipMemcpyHostToDevice);
+    if (err == hipSuccess) {   // a resample's rows (mg_plan_beam): the same rows within this pool, then the carry's
+        std::vector<PlanRow> br;
+        for (const StateRow &r : dst) br.push_back(PlanRow{r.off, r.off, r.esize, 0u});
+        const auto own = [&](const void *p, uint32_t esize) {
+            const uint64_t off = (uint64_t)((const char *)p - (const char *)T.P.mem);
+            br.push_back(PlanRow{off, off, esize, 0u});
+        };
+        own(T.beam_G, 8u); own(T.beam_P, 8u); own(T.beam_g, 8u);
+        own(T.beam_kp, 4u); own(T.beam_k, 4u); own(T.beam_ended, 4u);
+        err = hipMemcpy(T.beam_rows, br.data(), br.size() * sizeof(PlanRow), hipMemcpyHostToDevice);
+        T.beam_nrows = (int)br.size();
+    }
     if (err != hipSuccess) {
         pool_free(T.P);
         return set_err(-12, std::string(fn) + ": rollout pool setup: " + hipGetErrorString(err));
@@ -172,7 +189,7 @@ int rollout_reserve(mg_sim *s, RolloutPool &R, int M, const char *fn) {
 }
 
 int plan_rollouts(mg_sim *s, const MGState &F, const uint8_t *actions, int H, const mg_objective *obj, double *scores,
-                  int32_t *steps, int32_t *errors, hipStream_t st) {
+                  int32_t *steps, int32_t *errors, hipStream_t st, const LookCarry *carry) {
     if (!obj || obj->kind == MG_OBJ_FINAL) {
         const LookOut lo = {scores, steps, nullptr, nullptr, errors};
         HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, nullptr, st));
@@ -182,6 +199,7 @@ int plan_rollouts(mg_sim *s, const MGState &F, const uint8_t *actions, int H, co
     const LookOut lo = {nullptr, steps, nullptr, nullptr, errors};
     LookObj a = objective_args(s, obj);
     a.value = scores;
+    if (carry) a.carry = *carry;
     HIPC(mg_launch_lookahead(F, s->dlib, s->task, s->step_form, s->step_blk, s->max_steps, actions, H, lo, &a, st));
     return 0;
 }

@@ -1,7 +1,7 @@
 // mg_sim.h -- the simulator object behind the C ABI (include/magical_sim.h) and what the ABI's translation units share.
 // Each feature's entry points sit next to its kernels: create / seed / bind / reset / step / getters / destroy in
 // mg_sim.hip, snapshots in mg_snapshot.hip, mg_lookahead in mg_lookahead.hip, mg_plan in mg_plan.hip, mg_plan_cem in
-// mg_cem.hip (each with its _obj form beside it), replay and restack in mg_replay.hip.
+// mg_cem.hip (each with its _obj form beside it), mg_plan_beam in mg_beam.hip, replay and restack in mg_replay.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -90,6 +90,7 @@ int rollout_reserve(mg_sim *s, RolloutPool &R, int M, const char *fn);
 int objective_check(const mg_objective *o, const char *fn);
 LookObj objective_args(const mg_sim *s, const mg_objective *o);
 // mg_plan.hip: the rollouts of mg_plan and mg_plan_cem, plain (obj null or FINAL: scores = s_n) or traced (scores =
-// the objective's value) on the fan pool's first M envs
+// the objective's value) on the fan pool's first M envs; carry (mg_plan_beam, traced only): the objective continues
+// from launch to launch (LookCarry, mg_launch.h)
 int plan_rollouts(mg_sim *s, const MGState &F, const uint8_t *actions, int H, const mg_objective *obj, double *scores,
-                  int32_t *steps, int32_t *errors, hipStream_t st);
+                  int32_t *steps, int32_t *errors, hipStream_t st, const LookCarry *carry = nullptr);

@@ -11,11 +11,11 @@ include/magical_sim.h); importing this package does not require gym.
 """
 from .registry import (ALL_REGISTERED_ENVS, AVAILABLE_PREPROCESSORS, DEMO_ENVS_TO_TEST_ENVS_MAP, EnvName,  # noqa: F401
                        EnvSpec, lookup, update_magical_env_name)
-from .planning import CEMPolicy, Objective, ShootingPolicy, cem_step, plan_step  # noqa: F401
+from .planning import BeamPolicy, CEMPolicy, Objective, ShootingPolicy, cem_step, plan_step  # noqa: F401
 
 __all__ = ["ALL_REGISTERED_ENVS", "AVAILABLE_PREPROCESSORS", "DEMO_ENVS_TO_TEST_ENVS_MAP", "EnvName",
            "update_magical_env_name", "register_envs", "make", "make_vec", "ShootingPolicy", "plan_step",
-           "CEMPolicy", "cem_step", "Objective"]
+           "CEMPolicy", "cem_step", "Objective", "BeamPolicy"]
 
 _REGISTERED = False
 

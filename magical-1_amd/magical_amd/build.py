@@ -26,6 +26,7 @@ UNITS = {  # translation unit -> every header it includes, directly or not (one 
     "mg_sim.hip": _SIM + ["mg_math.h", "mg_phys.h", "mg_philox.h"],
     "mg_plan.hip": _SIM + ["mg_philox.h"],   # mg_plan, rollout pools, fan-out copy, reduction, sampler (rollouts: mg_look_*)
     "mg_cem.hip": _SIM + ["mg_cem.h", "mg_philox.h"],   # mg_plan_cem, its elite threshold and refit / draw kernels
+    "mg_beam.hip": _SIM + ["mg_beam.h", "mg_cem.h"],   # mg_plan_beam, its survivor selection and in-pool resample kernels
     "mg_snapshot.hip": _SIM,
     "mg_physics.hip": _LAUNCH,
     "mg_reset.hip": _PHYS + ["mg_reset.h"],

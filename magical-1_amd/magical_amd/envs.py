@@ -544,6 +544,55 @@ class VecMagicalEnv:
                 ordered[k] = res[k]
         return ordered
 
+    def plan_beam(self, actions, seg, survivors, details=False, objective=None):
+        """Beam search over action segments on the device (mg_plan_beam): plan() that prunes while it rolls out.
+        actions: [H, K, N] uint8 as plan()'s, H >= 1.  After every `seg` env-steps but the last segment's, each env
+        keeps its `survivors` slots with the highest value (the lower k first among equal values) where they are and
+        overwrites loser j, in ascending k, with a copy of survivor j mod survivors; slot k then goes on with its own
+        actions[h, k].  Returns fresh device tensors: 'best' i32[N] (the slot of the best lineage after the last
+        segment, the lowest k on ties), 'best_value' f64[N], 'first_action' u8[N], 'plan' u8[H, N] (that lineage's
+        actions); with details=True also 'plans' u8[H, K, N] (column (k, e): the actions of the lineage that ends in
+        slot k -- plan(plans) reproduces 'values', 'steps' and 'errors'), 'values' f64[K, N], 'steps' i32[K, N],
+        'errors' i32[K, N], 'depth_values' f64[D, K, N] (D = ceil(H / seg): the values after every segment, before its
+        resample) and 'parents' i32[D - 1, K, N] (the slot each slot was copied from; k itself for a survivor).
+        survivors == K or seg >= H is plan(actions).  The envs are untouched, as by plan().  objective (a
+        magical_amd.Objective): the values are the objective's, continued from segment to segment."""
+        obj = None if objective is None else self._objective_struct(objective, "plan_beam")
+        a = plan_actions(actions, self.num_envs)
+        H, K, n, dev = int(a.shape[0]), int(a.shape[1]), self.num_envs, self.device
+        seg, survivors = int(seg), int(survivors)
+        if H < 1:
+            raise ValueError("plan_beam: at least one step (H >= 1)")
+        if not 1 <= seg <= H:
+            raise ValueError(f"plan_beam: seg must be in [1, {H}], got {seg}")
+        if not 1 <= survivors <= K:
+            raise ValueError(f"plan_beam: survivors must be in [1, {K}], got {survivors}")
+        a = a.to(dev).contiguous()
+        D = -(-H // seg)
+        plans = torch.empty((H, K, n), dtype=torch.uint8, device=dev)
+        res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
+                                       ("best_value", torch.empty(n, dtype=torch.float64, device=dev)),
+                                       ("first_action", torch.empty(n, dtype=torch.uint8, device=dev)),
+                                       ("best_plan", torch.empty((H, n), dtype=torch.uint8, device=dev))])
+        if details:
+            res["values"] = torch.empty((K, n), dtype=torch.float64, device=dev)
+            res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+            res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+            res["depth_values"] = torch.empty((D, K, n), dtype=torch.float64, device=dev)
+            res["parents"] = torch.empty((D - 1, K, n), dtype=torch.int32, device=dev)
+        out = native.mg_plan_beam_out(**{k: v.data_ptr() for k, v in res.items() if v.numel()})
+        native.check(self.lib.mg_plan_beam(self.handle, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(plans.data_ptr()),
+                                           H, K, seg, survivors, None if obj is None else ctypes.byref(obj),
+                                           ctypes.byref(out), self._stream()))
+        self._last_plan = a   # (alive until the next call: the kernels read it on the stream)
+        ordered = collections.OrderedDict([(k, res[k]) for k in ("best", "best_value", "first_action")])
+        ordered["plan"] = res["best_plan"]
+        if details:
+            ordered["plans"] = plans
+            for k in ("values", "steps", "errors", "depth_values", "parents"):
+                ordered[k] = res[k]
+        return ordered
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.mg_destroy(self.handle)
@@ -665,6 +714,19 @@ class MagicalEnv:
         kw = {} if objective is None else {"objective": objective}
         res = self._vec.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key, step=step, **kw)
         return res["plan"][:, 0].cpu().numpy(), float(res["best_score"][0].item()), res["iter_best"][:, 0].cpu().numpy()
+
+    def plan_beam(self, actions, seg, survivors, objective=None):
+        """Beam search over action segments from the current state, which stays as it is (VecMagicalEnv.plan_beam for
+        this one env).  actions: [H, K] action ids.  Returns (plan, best_value, values): the best lineage's actions as a
+        uint8 array [H], its value, and every slot's value after the last segment as a float64 array [K]."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before plan_beam()")
+        a = torch.as_tensor(np.asarray(actions), dtype=torch.uint8)
+        if a.dim() != 2:
+            raise ValueError(f"plan_beam: actions must be [H, K], got {tuple(a.shape)}")
+        kw = {} if objective is None else {"objective": objective}
+        res = self._vec.plan_beam(a[:, :, None], seg, survivors, details=True, **kw)
+        return res["plan"][:, 0].cpu().numpy(), float(res["best_value"][0].item()), res["values"][:, 0].cpu().numpy()
 
     def get_state(self):
         """The env's whole state as bytes (a one-record snapshot blob, magical_amd.snapshot): physics, RNG, episode

@@ -262,6 +262,26 @@ class PipelinedVecEnv:
                 p[key].record_stream(self._caller())
         return out
 
+    def plan_beam(self, actions, seg, survivors, details=False, objective=None):
+        """VecMagicalEnv.plan_beam for the whole pool, per chunk as plan(): chunk k searches for its envs [bounds[k],
+        bounds[k + 1]) on its own stream, and the results are concatenated in env order."""
+        from .envs import plan_actions
+        kw = {} if objective is None else {"objective": objective}
+        a = plan_actions(actions, self.num_envs).to(self.device)
+        self.wait()
+        self._fork()
+        b, parts = self.bounds, []
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            with torch.cuda.stream(st):   # an env slice is strided: the chunk gets its own contiguous [H, K, m] copy
+                parts.append(sim.plan_beam(a[:, :, b[k]:b[k + 1]].contiguous(), seg, survivors, details=details, **kw))
+        self.wait()
+        out = collections.OrderedDict()
+        for key in parts[0]:
+            out[key] = torch.cat([p[key] for p in parts], dim=-1)   # envs are the last axis of every result
+            for p in parts:   # allocated on the chunks' streams, read here on the caller's
+                p[key].record_stream(self._caller())
+        return out
+
     def sample_plans(self, H, K, repeat=1, key=42, step=0, out=None):
         """u8[H, K, num_envs] random-shooting candidates (VecMagicalEnv.sample_plans per chunk).  Chunk k draws with
         key + k and numbers its envs from 0, as random_actions does: with J = ceil(H / repeat), the row [h, k] equals

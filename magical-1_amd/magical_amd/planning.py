@@ -155,3 +155,36 @@ class ShootingPolicy:
         self.last = self.env.plan(acts) if self.objective is None else self.env.plan(acts, objective=self.objective)
         self.t += 1
         return self.last["first_action"]
+
+
+class BeamPolicy:
+    """policy(obs) -> uint8 actions [N], ShootingPolicy's contract with beam search in place of whole-horizon rollouts:
+    every decision draws `candidates` random sequences of `horizon` env-steps per env (sample_plans, counters as
+    ShootingPolicy's: decision t draws from plan_step(t, ...) on), runs plan_beam() on them -- after every `seg`
+    env-steps each env keeps its `survivors` best partial rollouts and refills the other slots with copies of them --
+    and plays the first action of each env's best lineage.  objective: the Objective the slots are ranked by (None: the
+    score of the state they have reached)."""
+
+    def __init__(self, env, horizon, candidates, seg, survivors, repeat=1, key=42, objective=None):
+        if int(horizon) < 1 or int(candidates) < 1 or int(repeat) < 1:
+            raise ValueError("BeamPolicy: horizon, candidates and repeat must be at least 1")
+        if not 1 <= int(seg) <= int(horizon):
+            raise ValueError("BeamPolicy: seg must be in [1, horizon]")
+        if not 1 <= int(survivors) <= int(candidates):
+            raise ValueError("BeamPolicy: survivors must be in [1, candidates]")
+        self.env, self.horizon, self.candidates, self.repeat, self.key = env, int(horizon), int(candidates), int(repeat), key
+        self.seg, self.survivors = int(seg), int(survivors)
+        self.objective = as_objective(objective, "BeamPolicy")
+        self.t = 0
+        self.last = None   # the latest decision's plan_beam() result
+
+    def reset(self):
+        self.t = 0
+
+    def __call__(self, obs=None):
+        acts = self.env.sample_plans(self.horizon, self.candidates, self.repeat, self.key,
+                                     step=plan_step(self.t, self.horizon, self.candidates, self.repeat))
+        kw = {} if self.objective is None else {"objective": self.objective}
+        self.last = self.env.plan_beam(acts, self.seg, self.survivors, **kw)
+        self.t += 1
+        return self.last["first_action"]

@@ -2,6 +2,7 @@
 
     python tools/plan_bench.py --name MoveToRegion-Demo-LoRes4E-v0 --envs 1024
     python tools/plan_bench.py --name ClusterColour-Demo-LoResStack-v0 --envs 1024
+    python tools/plan_bench.py --beam --name ClusterColour-Demo-LoResStack-v0 --envs 1024   (mg_plan_beam: beam_bench)
 
 One simulator with an episode length no run reaches (nothing ends early), warmed up with random actions so contacts
 are live.  For every K (default 16, 64) at horizon H (default 16) each repetition times in turn, with HIP events on
@@ -89,6 +90,59 @@ def objective_bench(args, env, ks, timed, stats, res):
                                                    for key in ("plan", "return", "peak")})
 
 
+def beam_bench(args, env, ks, timed, stats, res):
+    """--beam: for every K, each repetition times in turn mg_plan and mg_plan_beam on the same candidates with segments
+    of --seg steps and K / 4 survivors (beam), with every slot surviving (beam_all: the same launches, nothing to
+    copy) and with one segment (beam_one: mg_plan's launches).  beam's plans are first checked to reproduce its values
+    under mg_plan.  copy_ms = beam - beam_all is what the resamples' copies cost, tails_ms = beam_all - beam_one the
+    extra launches; clone_store_gbs = the bytes the D - 1 resamples write -- (K - survivors) * N columns of a rollout's
+    share of the fan pool each -- over copy_ms."""
+    lib, dev, st, n, H, seg = env.lib, env.device, env._stream(), env.num_envs, args.horizon, args.seg
+    D = -(-H // seg)
+    free0 = torch.cuda.mem_get_info(dev)[0]
+    env.plan(env.sample_plans(1, max(ks)))   # the fan pool for the largest K: later calls allocate nothing
+    torch.cuda.synchronize()
+    per = (free0 - torch.cuda.mem_get_info(dev)[0]) / (max(ks) * n)
+    res.update(seg=seg, bytes_per_rollout=round(per, 1))
+    for K in ks:
+        B = max(1, K // 4)
+        acts = env.sample_plans(H, K, key=77, step=1000)
+        got = env.plan_beam(acts, seg, B, details=True)
+        ref = env.plan(got["plans"], details=True)
+        assert torch.equal(got["values"], ref["scores"]) and torch.equal(got["steps"], ref["steps"])
+        assert torch.equal(got["best"], ref["best"]) and bool((got["plans"] != acts).any())
+        f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+        best, value, first = torch.empty(n, **i32), torch.empty(n, **f64), torch.empty(n, dtype=torch.uint8, device=dev)
+        values, plans = torch.empty((K, n), **f64), torch.empty_like(acts)
+        pout = native.mg_plan_out(best=best.data_ptr(), best_score=value.data_ptr(), first_action=first.data_ptr(),
+                                  scores=values.data_ptr())
+        bout = native.mg_plan_beam_out(best=best.data_ptr(), best_value=value.data_ptr(), first_action=first.data_ptr(),
+                                       values=values.data_ptr())
+        ap_, pp = ctypes.c_void_p(acts.data_ptr()), ctypes.c_void_p(plans.data_ptr())
+
+        def plan():
+            native.check(lib.mg_plan(env.handle, ap_, H, K, ctypes.byref(pout), st))
+
+        def beam(sg, b):
+            native.check(lib.mg_plan_beam(env.handle, ap_, pp, H, K, sg, b, None, ctypes.byref(bout), st))
+
+        routes = {"plan": plan, "beam": lambda: beam(seg, B), "beam_all": lambda: beam(seg, K),
+                  "beam_one": lambda: beam(H, B)}
+        t = {key: [] for key in routes}
+        for r in range(args.warmup + args.reps):
+            row = {key: timed(fn) for key, fn in routes.items()}
+            if r >= args.warmup:
+                for key, v in row.items():
+                    t[key].append(v)
+        med = {key: statistics.median(v) for key, v in t.items()}
+        copy_ms, written = med["beam"] - med["beam_all"], (D - 1) * (K - B) * n * per
+        res["K"][str(K)] = dict({key: stats(v) for key, v in t.items()}, survivors=B,
+                                beam_over_plan=round(med["beam"] / med["plan"], 3),
+                                copy_ms=round(copy_ms, 4), tails_ms=round(med["beam_all"] - med["beam_one"], 4),
+                                copy_share_of_beam=round(copy_ms / med["beam"], 3),
+                                clone_store_gbs=round(written / (copy_ms * 1e-3) / 1e9, 1) if copy_ms > 0 else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--name", default="MoveToRegion-Demo-LoRes4E-v0")
@@ -101,6 +155,8 @@ def main():
     ap.add_argument("--objective", action="store_true",
                     help="time mg_plan against mg_plan_obj with FINAL, RETURN and PEAK instead (see objective_bench)")
     ap.add_argument("--gamma", type=float, default=0.99, help="--objective: the discount of RETURN and PEAK")
+    ap.add_argument("--beam", action="store_true", help="time mg_plan against mg_plan_beam instead (see beam_bench)")
+    ap.add_argument("--seg", type=int, default=4, help="--beam: env-steps per segment")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("plan_bench: no GPU (times are measured on the device or not at all)")
@@ -126,6 +182,11 @@ def main():
     res = {"name": args.name, "envs": n, "step_form": list(env.step_form()[:2]), "H": H, "reps": args.reps, "K": {}}
     if args.objective:
         objective_bench(args, env, ks, timed, stats, res)
+        print(json.dumps(res))
+        env.close()
+        return
+    if args.beam:
+        beam_bench(args, env, ks, timed, stats, res)
         print(json.dumps(res))
         env.close()
         return
