@@ -74,6 +74,27 @@ int mg_reset(mg_sim *sim, const uint8_t *mask_dev, void *stream);
  * max_episode_steps report done/reward/eval_score and are reset in place
  * (their observation is the first frame of the next episode) */
 int mg_step(mg_sim *sim, const uint8_t *actions_dev, void *stream);
+/* Several env-steps per call with one render (frame skip / action repeat; the committing twin of mg_lookahead below).
+ * actions_dev: device u8[R][N], step-major as mg_lookahead's (step h of env e at h*N + e), each in [0, 18);
+ * 1 <= R <= 4096.  steps_dev: device i32[N] or NULL.
+ * Per-env horizon: with left = max_episode_steps - episode_steps, env e runs n = R env-steps when
+ * max_episode_steps <= 0, else n = min(R, max(left, 1)) -- an env already past its end takes one step, as mg_step does.
+ * It runs n env-steps of BaseEnv.step physics with actions[0..n)[e], the operations of mg_step in the same order:
+ * afterwards the state, episode_steps (+n), error flags and RNG have the bits that n mg_step calls would leave.  Only
+ * step n can end the episode, so an env stops at its terminal step and its remaining R - n actions are ignored.
+ * Outputs (the bound buffers): done[e] = 1 iff step n ended the episode; eval_score[e] = the score at that step, else
+ * 0.0; reward[e] = (float)(r_1 + ... + r_n), summed left to right in double, one rounded add each, r_k being the
+ * double mg_step casts to float at step k (mg_objective's r_k; without the debug reward the sum is eval_score);
+ * steps_dev[e] = n.
+ * Auto-reset is mg_step's, unchanged, after the physics and for exactly the envs with done: in the kernel for the
+ * robot scenes without layout randomisation, from the next-layout shadow, or as a reset launch.  Then ONE render, as
+ * mg_step enqueues it: one frame is pushed per call and the window position advances by one, so frame stacks and
+ * window rings hold the frames seen at call boundaries, and a reset env's stack is filled with its first frame.  It
+ * works with materialised stacks, window rings, frames_only outputs and the unwrapped surface.  R = 1 is mg_step in
+ * every bound output and every state byte.  mg_enable_timing records a call like one mg_step call.
+ * Returns -22 and launches nothing for a null sim or actions_dev, R outside [1, 4096], or outputs not bound where
+ * mg_step would refuse. */
+int mg_step_seq(mg_sim *sim, const uint8_t *actions_dev, int32_t R, int32_t *steps_dev, void *stream);
 /* BaseEnv.render('rgb_array') of every env: device u8[N,2,384,384,3] (allo, ego) */
 int mg_render_full(mg_sim *sim, uint8_t *out_dev, void *stream);
 /* parity dumps: per env per body slot (px, py, angle, vx, vy, w): device f64[N,16,6];

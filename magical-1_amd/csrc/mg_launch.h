@@ -51,6 +51,15 @@ hipError_t launch_step_var(const MGState &S, const mg_library *L, TaskCfg cfg, i
 hipError_t mg_launch_step(const MGState &S, const mg_library *L, TaskCfg cfg, int form, int blk, int max_steps,
                           int auto_reset, const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
                           uint8_t *reset_mask, hipStream_t st);
+// mg_step_seq: up to R env-steps per env on S itself, then mg_step's tail once (defined in mg_seq.h, instantiated in
+// mg_seq_*.hip, dispatched in mg_physics.hip).  actions: u8[R][n_envs]; steps: i32[n_envs] or null
+template <int VAR, int BLK>
+hipError_t launch_step_seq_var(const MGState &S, const mg_library *L, TaskCfg cfg, int max_steps, int auto_reset,
+                               const uint8_t *actions, int R, float *reward, uint8_t *done, double *eval_score,
+                               int32_t *steps, uint8_t *reset_mask, hipStream_t st);
+hipError_t mg_launch_step_seq(const MGState &S, const mg_library *L, TaskCfg cfg, int form, int blk, int max_steps,
+                              int auto_reset, const uint8_t *actions, int R, float *reward, uint8_t *done,
+                              double *eval_score, int32_t *steps, uint8_t *reset_mask, hipStream_t st);
 // mg_lookahead: H env-steps of physics on S, the sim's scratch copy of the state, then the outputs of LookOut (the
 // device pointers of mg_lookahead_out; score is never null).  actions: u8[H][n_envs].  One compiled pair per pair of
 // the step kernel (defined in mg_lookahead.h, instantiated in mg_look_*.hip, dispatched in mg_lookahead.hip)

@@ -1,5 +1,5 @@
 // mg_sim.h -- the simulator object behind the C ABI (include/magical_sim.h) and what the ABI's translation units share.
-// Each feature's entry points sit next to its kernels: create / seed / bind / reset / step / getters / destroy in
+// Each feature's entry points sit next to its kernels: create / seed / bind / reset / step / step_seq / getters / destroy in
 // mg_sim.hip, snapshots in mg_snapshot.hip, mg_lookahead in mg_lookahead.hip, mg_plan in mg_plan.hip, mg_plan_cem in
 // mg_cem.hip (each with its _obj form beside it), mg_plan_beam in mg_beam.hip, replay and restack in mg_replay.hip.
 #pragma once

@@ -325,11 +325,10 @@ int mg_reset(mg_sim *s, const uint8_t *mask, void *stream) {
     return 0;
 }
 
-int mg_step(mg_sim *s, const uint8_t *actions, void *stream) {
-    if (!s || !actions) return set_err(-22, "mg_step: null argument");
-    if (!s->bound && s->preproc != MG_PREPROC_NONE) return set_err(-22, "mg_step: outputs not bound");
-    HIPC(hipSetDevice(s->device));
-    hipStream_t st = as_stream(stream);
+// The host part of mg_step and mg_step_seq: the fused_reset decision, the timing events, the physics launch (R = 0:
+// step_kernel on actions u8[N]; R >= 1: step_seq_kernel on actions u8[R][N], steps as mg_step_seq's), the reset phase on
+// the kernel's reset_mask, wstep and the one render
+static int step_call(mg_sim *s, const uint8_t *actions, int R, int32_t *steps, hipStream_t st) {
     TaskCfg cfg = {s->task, s->flags};
     // robot scenes without layout randomisation: the step kernel runs the auto-reset itself (mg_stepk.h)
     const bool layout = (s->flags & (MG_RAND_LAYOUT_MINOR | MG_RAND_LAYOUT_FULL)) != 0;
@@ -339,8 +338,12 @@ int mg_step(mg_sim *s, const uint8_t *actions, void *stream) {
     hipEvent_t *ev = nullptr;
     if (s->timing && s->ev_used + 4 <= s->ev.size()) { ev = &s->ev[s->ev_used]; s->ev_used += 4; }
     if (ev) HIPC(hipEventRecord(ev[0], st));
-    HIPC(mg_launch_step(s->main.S, s->dlib, cfg, s->step_form, s->step_blk, s->max_steps, s->auto_reset, actions, s->out.reward,
-                        s->out.done, s->out.eval_score, s->reset_mask, st));
+    if (R == 0)
+        HIPC(mg_launch_step(s->main.S, s->dlib, cfg, s->step_form, s->step_blk, s->max_steps, s->auto_reset, actions,
+                            s->out.reward, s->out.done, s->out.eval_score, s->reset_mask, st));
+    else
+        HIPC(mg_launch_step_seq(s->main.S, s->dlib, cfg, s->step_form, s->step_blk, s->max_steps, s->auto_reset, actions, R,
+                                s->out.reward, s->out.done, s->out.eval_score, steps, s->reset_mask, st));
     if (ev) HIPC(hipEventRecord(ev[1], st));
     if (s->auto_reset) {
         if (s->shadow_ok) {
@@ -356,6 +359,21 @@ int mg_step(mg_sim *s, const uint8_t *actions, void *stream) {
     if (s->preproc != MG_PREPROC_NONE) rc = render_lores(s, st, nullptr);
     if (ev) HIPC(hipEventRecord(ev[3], st));
     return rc;
+}
+
+int mg_step(mg_sim *s, const uint8_t *actions, void *stream) {
+    if (!s || !actions) return set_err(-22, "mg_step: null argument");
+    if (!s->bound && s->preproc != MG_PREPROC_NONE) return set_err(-22, "mg_step: outputs not bound");
+    HIPC(hipSetDevice(s->device));
+    return step_call(s, actions, 0, nullptr, as_stream(stream));
+}
+
+int mg_step_seq(mg_sim *s, const uint8_t *actions, int32_t R, int32_t *steps, void *stream) {
+    if (!s || !actions) return set_err(-22, "mg_step_seq: null argument");
+    if (R < 1 || R > 4096) return set_err(-22, "mg_step_seq: R must be in [1, 4096]");
+    if (!s->bound && s->preproc != MG_PREPROC_NONE) return set_err(-22, "mg_step_seq: outputs not bound");
+    HIPC(hipSetDevice(s->device));
+    return step_call(s, actions, R, steps, as_stream(stream));
 }
 
 int mg_bind_window(mg_sim *s, uint8_t *ring_allo, uint8_t *ring_ego, int32_t K) {

@@ -162,6 +162,7 @@ class VecMagicalEnv:
         self.reward = torch.zeros(n, dtype=torch.float32, device=dev)
         self.done = torch.zeros(n, dtype=torch.bool, device=dev)  # the C ABI writes u8 0/1: same bytes
         self.eval_score = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.seq_steps = None   # step_seq's info['steps'] i32[n] (not a bound output): allocated by the first step_seq
         self.target = torch.zeros((n, 4), dtype=torch.float64, device=dev) if self.spec.task == "PickAndPlace" else None
         self.frames_only = False
         self.reset_count = 0   # explicit reset() calls (magical_amd.dist checks its frame rings against it)
@@ -275,6 +276,38 @@ class VecMagicalEnv:
         if self.spec.preproc is None:
             self.render_full(out=self.full)
         return self._obs(), self.reward, self.done, {"eval_score": self.eval_score}
+
+    def step_seq(self, actions):
+        """Several env-steps per call with one render (frame skip; mg_step_seq).  actions: [R, N] uint8 (tensor or
+        array-like; [N] is R = 1), step h of env e at actions[h, e], 1 <= R <= 4096.  Env e runs n = min(R, steps left
+        in its episode, at least 1) env-steps, bit-identical to as many step() calls, stops at its terminal step and is
+        auto-reset as step() would; then every env is rendered ONCE, so the frame stacks hold the frames seen at call
+        boundaries.  Returns (obs, reward, done, info): reward is the float32 of the n rewards summed in double, done
+        says whether step n ended the episode, info holds 'eval_score' (the score at that step, else 0) and 'steps'
+        i32[N] (n).  step_seq(a[None]) is step(a)."""
+        a = torch.as_tensor(actions)
+        if a.dim() == 1:
+            a = a[None]
+        if a.dim() != 2 or a.shape[1] != self.num_envs:
+            raise ValueError(f"step_seq: actions must be [R, {self.num_envs}], got {tuple(a.shape)}")
+        if not (a.dtype == torch.uint8 and a.device == self.device and a.is_contiguous()):
+            a = a.to(self.device, torch.uint8).contiguous()
+        self._last_actions = a   # (alive until the next call: the kernel reads it on the stream)
+        if self.seq_steps is None:   # (no fill: the kernel writes every env's element)
+            self.seq_steps = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        native.check(self.lib.mg_step_seq(self.handle, ctypes.c_void_p(a.data_ptr()), int(a.shape[0]),
+                                          ctypes.c_void_p(self.seq_steps.data_ptr()), self._stream()))
+        if self.spec.preproc is None:
+            self.render_full(out=self.full)
+        return self._obs(), self.reward, self.done, {"eval_score": self.eval_score, "steps": self.seq_steps}
+
+    def step_repeat(self, actions, repeat):
+        """step_seq with every env's action held for `repeat` env-steps (action repeat).  actions: [N] uint8."""
+        a = torch.as_tensor(actions)
+        if a.dim() != 1 or a.shape[0] != self.num_envs:
+            raise ValueError(f"step_repeat: actions must be [{self.num_envs}], got {tuple(a.shape)}")
+        a = a.to(self.device, torch.uint8)
+        return self.step_seq(a[None].expand(int(repeat), -1).contiguous())
 
     def random_actions(self, step, key=42, out=None):
         out = out if out is not None else torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
@@ -661,6 +694,19 @@ class MagicalEnv:
         d = bool(done[0].item())
         score = float(info["eval_score"][0].item())
         return self._np_obs(obs), float(rew[0].item()), d, {"eval_score": score}
+
+    def step_seq(self, actions):
+        """Run `actions` (a sequence of 1 .. 4096 action ids) as env-steps, stopping at the episode's end, and render
+        once: (obs, summed reward, done, {'eval_score', 'steps': env-steps run}) -- VecMagicalEnv.step_seq for this
+        one env."""
+        if self._episode_steps is None:
+            raise RuntimeError("call reset() before step_seq()")
+        a = torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1)
+        obs, rew, done, info = self._vec.step_seq(a)
+        n = int(info["steps"][0].item())
+        self._episode_steps += n
+        return self._np_obs(obs), float(rew[0].item()), bool(done[0].item()), \
+            {"eval_score": float(info["eval_score"][0].item()), "steps": n}
 
     def score(self):
         """The task's score (score_on_end_of_traj) of the current state, at any point of the episode; step() reports

@@ -91,7 +91,8 @@ class PipelinedVecEnv:
         # done[k][slot]: chunk k finished the step that read action slot `slot`
         self.done_ev = [[None, None] for _ in range(chunks)]
         self.t = 0
-        self.reset_count = 0      # explicit reset() calls (magical_amd.dist checks its frame rings against it)
+        self.seq_steps = None     # step_seq's info['steps'] for the whole pool (allocated by the first call)
+        self.reset_count = 0     # explicit reset() calls (magical_amd.dist checks its frame rings against it)
         self.target = self.buffers.get("target")
         # the observation's float32 target columns, converted on each chunk's stream right after its step (a
         # conversion on the caller's stream inside step() would read the target before the chunk wrote it)
@@ -176,6 +177,40 @@ class PipelinedVecEnv:
         self._last = [self.done_ev[k][slot] for k in range(self.chunks)]
         self.t += 1
         return self._obs(), self.buffers["reward"], self.buffers["done"], {"eval_score": self.buffers["eval_score"]}
+
+    def step_seq(self, actions):
+        """VecMagicalEnv.step_seq for the whole pool: actions [R, num_envs] ([num_envs]: R = 1); chunk k runs its
+        columns [bounds[k], bounds[k + 1]) as one mg_step_seq call on its own stream, as step() does, and like step()
+        the call only enqueues: a chunk's outputs are complete after wait(k) / wait().  info holds 'eval_score' and
+        'steps' i32[num_envs]."""
+        a = torch.as_tensor(actions)
+        if a.dim() == 1:
+            a = a[None]
+        if a.dim() != 2 or a.shape[1] != self.num_envs:
+            raise ValueError(f"step_seq: actions must be [R, {self.num_envs}], got {tuple(a.shape)}")
+        a = a.to(self.device, torch.uint8)
+        b = self.bounds
+        if self.seq_steps is None:   # the chunks' info['steps'] as slices of one pool tensor
+            self.seq_steps = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+            for k, sim in enumerate(self.sims):
+                sim.seq_steps = self.seq_steps[b[k]:b[k + 1]]
+        # a column slice is strided: every chunk gets its own contiguous [R, m] copy, made on the caller's stream
+        parts = [a[:, b[k]:b[k + 1]].contiguous() for k in range(self.chunks)]
+        self._fork()
+        self._last = []
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            parts[k].record_stream(st)
+            with torch.cuda.stream(st):
+                sim.step_seq(parts[k])
+                if self.target_f is not None:
+                    self.target_f[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
+                    if self._target_out is not None:
+                        self._target_out[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
+            ev = torch.cuda.Event()
+            ev.record(st)
+            self._last.append(ev)
+        return self._obs(), self.buffers["reward"], self.buffers["done"], \
+            {"eval_score": self.buffers["eval_score"], "steps": self.seq_steps}
 
     def snapshot(self):
         """The pool's state as a `magical_amd.snapshot.PoolSnapshot`: one blob per chunk, taken on the chunk's own

@@ -36,10 +36,15 @@ class MagicalVecEnv(_VecEnvBase):
     metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, env_name, num_envs, device="cuda:0", seeds=None, base_seed=0, monitor=True,
-                 as_tensors=False, debug_reward=None, max_episode_steps=None):
+                 as_tensors=False, debug_reward=None, max_episode_steps=None, frame_skip=1):
         self.venv = VecMagicalEnv(env_name, num_envs, device=device, seeds=seeds, base_seed=base_seed,
                                   auto_reset=False, debug_reward=debug_reward, max_episode_steps=max_episode_steps)
         self.num_envs = self.venv.num_envs
+        # frame skip / action repeat: every action is held for frame_skip env-steps (one mg_step_seq call, one render);
+        # rewards are summed over them, episode lengths count env-steps, an episode's last call may run fewer
+        self.frame_skip = int(frame_skip)
+        if self.frame_skip < 1:
+            raise ValueError("MagicalVecEnv: frame_skip must be >= 1")
         self.observation_space = self.venv.observation_space
         self.action_space = self.venv.action_space
         self.render_mode = "rgb_array"
@@ -68,9 +73,13 @@ class MagicalVecEnv(_VecEnvBase):
         self._actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions)
 
     def step_wait(self):
-        obs, rew, done, info = self.venv.step(self._actions)
+        if self.frame_skip == 1:
+            obs, rew, done, info = self.venv.step(self._actions)
+            self._ep_len += 1
+        else:   # (auto_reset=False: the observation of a finished env is the frame of its terminal state)
+            obs, rew, done, info = self.venv.step_repeat(self._actions, self.frame_skip)
+            self._ep_len += info["steps"]
         self._ep_return += rew.to(torch.float64)
-        self._ep_len += 1
         scores = info["eval_score"].cpu().numpy()
         dones = done.cpu().numpy().astype(bool)
         rewards = rew.cpu().numpy().astype(np.float32)
