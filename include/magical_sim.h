@@ -106,6 +106,12 @@ int mg_get_bodies(mg_sim *sim, double *out_dev, int32_t *counts_dev, void *strea
  * u64[N,48,2] = the contacts' feature hashes; rows past the env's active count are zero.  Test hook of the
  * parity suite (the reference has no such call: pymunk exposes the same data as Arbiter.contact_point_set) */
 int mg_get_arbiters(mg_sim *sim, double *out_dev, uint64_t *hash_dev, void *stream);
+/* parity dump of every env's RNG, the numpy-legacy MT19937 that resets draw layouts from: key_dev u32[N,624] and
+ * pos_dev i32[N] are numpy's RandomState.get_state()[1:3] (pos == 624: the next draw regenerates the key).  Read-only
+ * and stream-ordered (one small copy kernel); it reads the main state, the rows mg_snapshot records -- what the env's
+ * next in-place reset would draw from, not the next-layout shadow's copy running ahead of it.  Test hook
+ * (tests/test_rng_stream.py follows the stream across its regenerations in every reset path) */
+int mg_get_rng(mg_sim *sim, uint32_t *key_dev, int32_t *pos_dev, void *stream);
 /* set body `body` of env `env` to (x, y, angle) like pymunk's Body.position / Body.angle setters
  * (geom.py:362-384 pm_shift_bodies applies them); for parity tests that place blocks before a step */
 int mg_set_body_pose(mg_sim *sim, int env, int body, double x, double y, double angle, void *stream);
@@ -128,6 +134,17 @@ int mg_step_form(const mg_sim *sim, int32_t *out);
 /* self-test of the device's correctly rounded sin/cos (the physics and render transforms use it):
  * device f64 x[n] -> sin, cos */
 int mg_selftest_sincos(const double *x_dev, double *sin_dev, double *cos_dev, int n, void *stream);
+/* self-test of the device MT19937's three regeneration ("twist") paths.  One wavefront per seed seeds a scratch
+ * generator as mg_seed does (seeds_dev: device u32[n]) and writes the tempered 32-bit words of its next ndraws draws
+ * to out_dev, device u32[n][ndraws] -- RandomState(seed).bytes(4 * ndraws) read as little-endian u32.  mode 0: one
+ * lane draws over the state in HBM (the auto-reset fused into the robot scenes' step kernels); 1: the state sits in
+ * LDS and the wavefront's 64 lanes draw together (the reset kernel); 2: the same with only lanes 0-36 active (the LDS
+ * twist's serial branch) -- lane 0 writes out_dev[0 .. n*ndraws), lane 36 a second copy to out_dev[n*ndraws ..
+ * 2*n*ndraws), so in mode 2 out_dev holds u32[2][n][ndraws].  The scratch state is allocated and freed by the call,
+ * which waits for the kernel on `stream`; no sim is involved.
+ * Returns -22 and launches nothing for a null seeds_dev or out_dev, n outside [1, 4096], ndraws outside [1, 8192] or
+ * a mode other than 0, 1, 2 */
+int mg_selftest_mt(const uint32_t *seeds_dev, int n, int ndraws, int mode, uint32_t *out_dev, void *stream);
 /* per-kernel timing of the next max_steps mg_step calls (hipEvents on the launch stream); 0 disables */
 int mg_enable_timing(mg_sim *sim, int max_steps);
 /* out[0] = total ms in the physics/step kernel, out[1] = total ms in the render kernel,

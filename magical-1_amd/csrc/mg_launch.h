@@ -38,6 +38,10 @@ struct RenderOut {
 };
 
 hipError_t mg_launch_seed(const MGState &S, const uint32_t *seeds_dev, hipStream_t st);
+// mg_selftest_mt: one wavefront per seed draws ndraws words through mt_next32's twist path `mode` (0 HBM, 1 LDS with
+// 64 lanes, 2 LDS with lanes 0-36).  key / pos: scratch u32[624][n] / i32[n]; out: u32[n][ndraws], mode 2 twice that
+hipError_t mg_launch_selftest_mt(const uint32_t *seeds_dev, int n, int ndraws, int mode, uint32_t *key, int32_t *pos,
+                                 uint32_t *out, hipStream_t st);
 // max_waves > 0 (masked launches only): at most that many wavefronts, each resetting the masked envs of its
 // grid-stride range in turn; 0: one wavefront per env
 hipError_t mg_launch_reset(const MGState &S, const mg_library *L, TaskCfg cfg, const uint8_t *mask, hipStream_t st,

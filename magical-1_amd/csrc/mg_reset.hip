@@ -47,6 +47,50 @@ reset_kernel(MGState S, const mg_library *__restrict__ L, TaskCfg cfg, const uin
     }
 }
 
+// self-test of mt_next32's three twist paths (mg_selftest_mt; tests/test_rng_stream.py compares the words with
+// numpy's): wavefront e seeds env e of a scratch state (S.mt_key [624][n], S.mt_pos [n], S.N = S.n_envs = n) with
+// mt_seed and writes ndraws tempered words to out[e][..].  MODE 0: lane 0 alone draws over HBM, as a fused reset in
+// the step kernel does; 1: the state goes to LDS as in reset_kernel and all 64 lanes draw together; 2: the same with
+// lanes 0-36 only (mt_twist_lds's serial branch), lane 36 writing a second copy n * ndraws words further on
+template <int MODE>
+__global__ void __launch_bounds__(64) selftest_mt_kernel(MGState S, const uint32_t *__restrict__ seeds, int ndraws,
+                                                         uint32_t *__restrict__ out) {
+    __shared__ uint32_t mt[625];
+    const int lane = (int)threadIdx.x, e = (int)blockIdx.x;
+    if (e >= S.n_envs) return;
+    uint32_t *o = out + (size_t)e * (size_t)ndraws;
+    if (lane == 0) mt_seed(S, e, seeds[e]);
+    if constexpr (MODE == 0) {
+        if (lane == 0)
+            for (int k = 0; k < ndraws; k++) o[k] = mt_next32(S, e);
+    } else {
+        __threadfence_block();   // lane 0's seeded words, read by every lane
+        __syncthreads();
+        for (int i = lane; i < 624; i += 64) mt[i] = S.mt_key[(size_t)i * S.N + e];
+        if (lane == 0) mt[624] = (uint32_t)S.mt_pos[e];
+        __syncthreads();
+        MGState V = S;
+        V.mt_lds = mt;
+        if (MODE == 1 || lane < 37) {
+            uint32_t *o2 = o + (size_t)S.n_envs * (size_t)ndraws;
+            for (int k = 0; k < ndraws; k++) {
+                const uint32_t y = mt_next32(V, e);
+                if (lane == 0) o[k] = y;
+                if (MODE == 2 && lane == 36) o2[k] = y;
+            }
+        }
+    }
+}
+
+hipError_t mg_launch_selftest_mt(const uint32_t *seeds_dev, int n, int ndraws, int mode, uint32_t *key, int32_t *pos,
+                                 uint32_t *out, hipStream_t st) {
+    MGState S = {};
+    S.n_envs = n; S.N = n; S.mt_key = key; S.mt_pos = pos;
+    auto k = mode == 0 ? selftest_mt_kernel<0> : mode == 1 ? selftest_mt_kernel<1> : selftest_mt_kernel<2>;
+    hipLaunchKernelGGL(k, dim3(n), dim3(64), 0, st, S, seeds_dev, ndraws, out);
+    return hipGetLastError();
+}
+
 static int grid64(const MGState &S) { return (S.n_envs + 63) / 64; }
 
 hipError_t mg_launch_seed(const MGState &S, const uint32_t *seeds_dev, hipStream_t st) {

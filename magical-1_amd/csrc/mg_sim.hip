@@ -66,6 +66,15 @@ __global__ void __launch_bounds__(64) arbiters_kernel(MGState S, double *out, ui
     }
 }
 
+// every env's MT19937 state as numpy's get_state()[1:3]: key[e][624] (the state keeps it word-major), pos[e]
+__global__ void __launch_bounds__(256) rng_kernel(MGState S, uint32_t *__restrict__ key, int32_t *__restrict__ pos) {
+    const size_t n = (size_t)S.n_envs, t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= 624 * n) return;
+    const size_t i = t / n, e = t % n;
+    key[e * 624 + i] = S.mt_key[i * (size_t)S.N + e];
+    if (i == 0) pos[e] = S.mt_pos[e];
+}
+
 __global__ void __launch_bounds__(64) errors_kernel(MGState S, int32_t *out) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= S.n_envs) return;
@@ -438,6 +447,37 @@ int mg_get_arbiters(mg_sim *s, double *out, uint64_t *hash, void *stream) {
     HIPC(hipSetDevice(s->device));
     hipLaunchKernelGGL(arbiters_kernel, dim3(grid64(s)), dim3(64), 0, as_stream(stream), s->main.S, out, hash);
     HIPC(hipGetLastError());
+    return 0;
+}
+
+int mg_get_rng(mg_sim *s, uint32_t *key, int32_t *pos, void *stream) {
+    if (!s || !key || !pos) return set_err(-22, "mg_get_rng: null argument");
+    HIPC(hipSetDevice(s->device));
+    const size_t total = (size_t)624 * (size_t)s->main.S.n_envs;
+    hipLaunchKernelGGL(rng_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), s->main.S, key, pos);
+    HIPC(hipGetLastError());
+    return 0;
+}
+
+int mg_selftest_mt(const uint32_t *seeds, int n, int ndraws, int mode, uint32_t *out, void *stream) {
+    if (!seeds || !out) return set_err(-22, "mg_selftest_mt: null argument");
+    if (n < 1 || n > 4096 || ndraws < 1 || ndraws > 8192)
+        return set_err(-22, "mg_selftest_mt: n must be in [1, 4096] and ndraws in [1, 8192]");
+    if (mode < 0 || mode > 2) return set_err(-22, "mg_selftest_mt: mode must be 0, 1 or 2");
+    // a scratch MT19937 state of its own (never a sim's), freed once the kernel has finished
+    uint32_t *key = nullptr;
+    int32_t *pos = nullptr;
+    if (hipMalloc((void **)&key, sizeof(uint32_t) * 624 * (size_t)n) != hipSuccess)
+        return set_err(-12, "mg_selftest_mt: hipMalloc");
+    if (hipMalloc((void **)&pos, sizeof(int32_t) * (size_t)n) != hipSuccess) {
+        (void)hipFree(key);
+        return set_err(-12, "mg_selftest_mt: hipMalloc");
+    }
+    hipError_t err = mg_launch_selftest_mt(seeds, n, ndraws, mode, key, pos, out, as_stream(stream));
+    if (err == hipSuccess) err = hipStreamSynchronize(as_stream(stream));
+    (void)hipFree(key);
+    (void)hipFree(pos);
+    HIPC(err);
     return 0;
 }
 

@@ -333,6 +333,15 @@ class VecMagicalEnv:
                                             ctypes.c_void_p(counts.data_ptr()), self._stream()))
         return out, counts
 
+    def rng_state(self):
+        """every env's MT19937 state as numpy's RandomState.get_state()[1:3]: (key uint32 [N, 624], pos int32 [N])
+        device tensors (mg_get_rng; pyoracle.OracleEnv.rng_state() per env)"""
+        key = torch.empty((self.num_envs, 624), dtype=torch.uint32, device=self.device)
+        pos = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        native.check(self.lib.mg_get_rng(self.handle, ctypes.c_void_p(key.data_ptr()), ctypes.c_void_p(pos.data_ptr()),
+                                         self._stream()))
+        return key, pos
+
     def step_form(self):
         """(form, envs per workgroup, (bodies, shapes, constraints, arbiter slots) caps) of the step kernel
         (mg_step_form)"""

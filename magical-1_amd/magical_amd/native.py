@@ -16,7 +16,8 @@ EXPORTS = ["mg_create", "mg_bind_outputs", "mg_reset", "mg_step", "mg_render_ful
            "mg_set_body_pose", "mg_get_errors", "mg_seed", "mg_random_actions", "mg_num_envs", "mg_step_form", "mg_enable_timing", "mg_read_timing",
            "mg_set_episode_steps", "mg_selftest_sincos", "mg_replay_lores", "mg_restack", "mg_restack_window", "mg_bind_window",
            "mg_window_start", "mg_snapshot_bytes", "mg_snapshot", "mg_restore", "mg_lookahead", "mg_plan", "mg_plan_sample",
-           "mg_plan_cem", "mg_lookahead_obj", "mg_plan_obj", "mg_plan_cem_obj", "mg_plan_beam", "mg_step_seq", "mg_destroy",
+           "mg_plan_cem", "mg_lookahead_obj", "mg_plan_obj", "mg_plan_cem_obj", "mg_plan_beam", "mg_step_seq", "mg_get_rng",
+           "mg_selftest_mt", "mg_destroy",
            "mg_last_error"]
 PLAN_MAX_ROLLOUTS = 262144   # MG_PLAN_MAX_ROLLOUTS: K * num_envs of one mg_plan call
 OBJ_FINAL, OBJ_RETURN, OBJ_PEAK = 0, 1, 2   # MG_OBJ_*
@@ -109,6 +110,8 @@ def load():
     if hasattr(lib, "mg_step_form"):
         lib.mg_step_form.argtypes = [vp, vp]
     lib.mg_selftest_sincos.argtypes = [vp, vp, vp, i32, vp]
+    lib.mg_get_rng.argtypes = [vp, vp, vp, vp]
+    lib.mg_selftest_mt.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.mg_enable_timing.argtypes = [vp, i32]
     lib.mg_read_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
     lib.mg_set_episode_steps.argtypes = [vp, vp, vp]

@@ -415,6 +415,14 @@ class PipelinedVecEnv:
         self.wait()
         return torch.cat([sim.errors() for sim in self.sims])
 
+    def rng_state(self):
+        """VecMagicalEnv.rng_state of the whole pool: (key uint32 [num_envs, 624], pos int32 [num_envs])"""
+        self.wait()
+        parts = [sim.rng_state() for sim in self.sims]
+        # (torch.cat has no uint32 kernel: the keys are joined as int32 bits, as plan_cem's uint16 weights are)
+        key = torch.cat([k.view(torch.int32) for k, _ in parts]).view(torch.uint32)
+        return key, torch.cat([p for _, p in parts])
+
     def enable_timing(self, steps):
         """Per-chunk HIP-event timing of the kernels (mg_enable_timing on every chunk's simulator)."""
         self.wait()
