@@ -235,6 +235,79 @@ int mg_snapshot(mg_sim *sim, const int32_t *envs, int32_t n, uint8_t *blob_dev, 
  * and eval_score describe a step, not a state, and stay as they are.  The many-block tasks' next-layout shadow of
  * the restored envs is prepared again from the restored RNG state, as after a masked mg_reset. */
 int mg_restore(mg_sim *sim, const uint8_t *blob_dev, const int32_t *envs, const int32_t *recs, int32_t n, void *stream);
+/* Explicit scenes: an env's layout as data (SURVEY.md section 8(b) planned it as mg_set_layouts).  One fixed-size
+ * plain-data record per env, little-endian, no pointers: a [N] array of it is one flat device buffer (sizeof(mg_scene)
+ * = 792 bytes, 8-byte aligned rows) and one numpy structured array (magical_amd.native.SCENE_DTYPE).  The arena is
+ * implicit; ent[] holds the entities after it in the order the task's reset instantiates them:
+ *   MoveToRegion: goal, robot.  MoveToCorner: robot, block.  ClusterColour / ClusterShape, MakeLine: blocks, robot.
+ *   FindDupe: goal, outer blocks, query block, robot.  FixColour: nr goals, nr blocks, robot.  PickAndPlace: robot,
+ *   3 blocks.  MatchRegions: goal, blocks, robot.
+ * Roles are not part of the record; mg_reset_scene derives them as the task's reset does (FindDupe: 1 iff type and colour
+ * equal the query block's, else 2; FixColour: 1 iff block i's colour equals region i's, else 2; MatchRegions: 1 iff the
+ * colour equals the goal's, else 2; other tasks 0), and PickAndPlace's target ids from the target entity's type and
+ * colour.  (The structs carry a tag so that they may hold arrays; the layout is the declaration's, no padding.) */
+typedef struct mg_scene_ent {
+    int32_t kind;      /* 1 goal region, 2 robot, 3 block: the MG_ENT_* values of magical-1_amd/csrc/mg_common.h */
+    int32_t type;      /* blocks: MG_SHAPE_* (square 1, pentagon 2, circle 5, star 6 are the types resets draw); else 0 */
+    int32_t colour;    /* blocks and goals: MG_COL_RED 0, GREEN 1, BLUE 2, YELLOW 3; robot: ignored on input, MG_COL_GREY
+                          (4) on output */
+    int32_t flags;     /* bit 0: disabled -- collides with nothing for the episode (what a failed placement retry leaves
+                          behind: MG_GROUP_OFF / goal enabled = 0); other bits 0 */
+    double  x, y;      /* robot, block: root body position; goal: the sensor's CENTRE */
+    double  angle;     /* robot, block: root body angle; goal: 0 */
+    double  h, w;      /* goal only; else 0 */
+} mg_scene_ent;
+typedef struct mg_scene {
+    int32_t n_ents;        /* entities after the arena, 1 .. 13 */
+    int32_t target_ent;    /* PickAndPlace: index into ent[] of the block to place; else -1 on output, ignored on input */
+    double  pv[5];         /* physics variables in PhysVar declaration order: robot pos / rot joint max force, robot
+                              finger max force, shape trans / rot joint max force (defaults 3, 1, 4, 1.5, 0.1) */
+    double  target_xy[2];  /* PickAndPlace target position; else 0 on output, ignored on input */
+    mg_scene_ent ent[13];  /* MG_MAX_ENTS - 1; entries past n_ents are zero on output, ignored on input */
+} mg_scene;
+/* Every env's CURRENT layout -> scenes_dev, device mg_scene[num_envs], 8-byte aligned: the entity table (kind, type,
+ * colour, enabled state), each entity's pose from its root body as it stands (mid-episode poses, not the reset's), goal
+ * centre, h and w, pv, PickAndPlace's target.  One small read-only kernel, stream-ordered, like mg_get_rng; it touches
+ * nothing in the sim. */
+int mg_get_scene(mg_sim *sim, mg_scene *scenes_dev, void *stream);
+/* A masked reset, as mg_reset(mask) is, whose layout comes from scenes_dev[e] (device mg_scene[num_envs], 8-byte
+ * aligned, read only) instead of the task's constants and the RNG.  The state env e is left in is what the task's reset
+ * leaves for a variant without layout randomisation: episode state, arbiter table, stamp, curr_dt, robot targets and
+ * error bit 2 cleared, pv from the record, every entity instantiated once, in record order, directly at its pose
+ * (velocities zero; the robot's eye bodies, which the reset instantiates at the origin and the layout sampler drags along
+ * with the robot, sit where a rigid move of the task's Demo robot pose to the given pose puts them -- at the origin for
+ * the Demo pose itself; nothing reads their position), a goal's centre stored as given, disabled entities folded into
+ * MG_GROUP_OFF, PickAndPlace's bound target output written.  The env's MT19937 rows are neither read nor written, and
+ * the next-layout shadow and its pending work are left alone: the env's next auto-reset draws what it would have drawn.
+ *
+ * Validation runs on the device, per env, and is complete before any write to that env.  status_dev (required, device
+ * i32[num_envs]) receives, the lowest code that applies:
+ *    0 built;  -1 not selected by the mask;
+ *    1 entity count or kind order is not the task's (orders above; block counts: Cluster >= 7, MakeLine >= 3, FindDupe
+ *      >= 2 outer blocks plus the query, FixColour >= 2 regions with as many blocks, MatchRegions >= 1 block and at
+ *      least one of the goal's colour, PickAndPlace exactly 3, MoveToCorner exactly 1);
+ *    2 a field is out of range: an enum outside its set, a type / h / w / goal angle that must be 0 and is not, unknown
+ *      flag bits, a non-finite number, |x| or |y| > 1, |angle| > 100, a goal's h or w outside [0.1, 0.8] (0.8 is
+ *      RAND_GOAL_MAX_SIZE, the largest goal any variant draws: the render classes are sized for it), pv[i] not finite
+ *      or <= 0, PickAndPlace's target_xy not finite or beyond +-1;
+ *    3 the scene does not fit the handle: bodies, shapes and constraints counted from the record must be <= the slot
+ *      caps of the handle's task and rand_flags (what mg_step_form reports for form 0), and EQUAL to them when the
+ *      handle runs step form 5 or 6, whose constraint lists are compiled (a star on a MoveToCorner handle created
+ *      without the shape-type flag is refused, as is a ninth block on a Cluster handle created without the count flag);
+ *    4 PickAndPlace's target_ent is not one of the blocks.
+ * An env with status > 0 is left completely untouched (state, flags, frames).
+ * check = 1: afterwards every built env runs the reset's own overlap test on every enabled entity (the shape queries of
+ * the layout sampler, with the task's ignore rules: FindDupe's query block and goal ignore each other, FixColour's
+ * blocks ignore their own region), one wavefront per env; an env with any hit gets error flags 2 | 64 (PlacementError,
+ * as a failed layout draw does).  It is still built and its status stays 0.  check = 0 launches no such work.
+ * Then one LoRes render of the built envs, exactly as mg_reset(mask) renders: their frame stacks / window-ring slots are
+ * filled with the first frame, the render's per-episode scratch starts over, other envs' outputs keep their bytes; the
+ * window position does not advance.  Works with materialised stacks, window rings, frames_only outputs and the
+ * unwrapped surface.  Everything is enqueued on `stream`; no host sync.
+ * Returns -22 and launches nothing for a null sim, scenes_dev or status_dev, a scenes_dev that is not 8-byte aligned,
+ * check outside {0, 1}, or outputs not bound where mg_reset would refuse.  mask_dev NULL = all envs. */
+int mg_reset_scene(mg_sim *sim, const mg_scene *scenes_dev, const uint8_t *mask_dev, int32_t check,
+                   int32_t *status_dev, void *stream);
 /* Lookahead: "what happens if these envs run these H actions", without touching the envs.  Caller-owned device
  * outputs: */
 typedef struct {

@@ -1,7 +1,8 @@
 // mg_sim.h -- the simulator object behind the C ABI (include/magical_sim.h) and what the ABI's translation units share.
 // Each feature's entry points sit next to its kernels: create / seed / bind / reset / step / step_seq / getters / destroy in
 // mg_sim.hip, snapshots in mg_snapshot.hip, mg_lookahead in mg_lookahead.hip, mg_plan in mg_plan.hip, mg_plan_cem in
-// mg_cem.hip (each with its _obj form beside it), mg_plan_beam in mg_beam.hip, replay and restack in mg_replay.hip.
+// mg_cem.hip (each with its _obj form beside it), mg_plan_beam in mg_beam.hip, replay and restack in mg_replay.hip,
+// explicit scenes (mg_get_scene, mg_reset_scene) in mg_scene.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -56,6 +57,7 @@ struct mg_sim {
     int step_form = 0;     // step kernel form and envs per workgroup: a compiled pair of mg_stepforms.h
     int step_blk = 0;
     uint8_t *reset_mask = nullptr;   // device u8[N]: envs to auto-reset after the step
+    uint8_t *scene_built = nullptr;  // device u8[N]: envs the latest mg_reset_scene built (its render's mask)
     // snapshots (mg_snapshot.hip; layout: mg_snapshot.h)
     SnapRow *srows = nullptr;        // device table of a record's rows: the state rows and the per-env items layout() keeps out of them
     int nsrows = 0;

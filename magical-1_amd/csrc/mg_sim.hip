@@ -237,6 +237,9 @@ static int sim_init(mg_sim *s, const mg_config *cfg) {
     s->step_blk = step_pick_blk(s->step_form, cfg->num_envs, cus, env_int("MG_STEP_BLK", 0), env_int("MG_STEP_BLK0", 0));
     if (hipMalloc((void **)&s->reset_mask, (size_t)N) != hipSuccess) return set_err(-12, "mg_create: hipMalloc mask");
     HIPC(hipMemset(s->reset_mask, 0, (size_t)N));
+    // (no fill: mg_reset_scene's build kernel writes every env's byte before its render reads it, and one more launch
+    // here moves the first step's workgroups to other CUs -- DESIGN.md section 4, step sequences, last paragraph)
+    if (hipMalloc((void **)&s->scene_built, (size_t)N) != hipSuccess) return set_err(-12, "mg_create: hipMalloc mask");
     // next-layout shadow: the many-block tasks, whose rejection-sampled layouts make a reset long (the
     // robot scenes reset in ~0.03 ms); MG_RESET_PREFETCH=0/1 overrides
     bool prefetch = s->auto_reset && s->task != MG_TASK_MOVE_TO_REGION && s->task != MG_TASK_MOVE_TO_CORNER;
@@ -592,7 +595,8 @@ void mg_destroy(mg_sim *s) {
     for (hipEvent_t e : {s->ev_copied, s->ev_prepared, s->ev_snap})
         if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(s->snap_stage);
-    for (void *p : {(void *)s->rows, (void *)s->pend, (void *)s->snap_dev, (void *)s->srows, (void *)s->dlib, (void *)s->reset_mask})
+    for (void *p : {(void *)s->rows, (void *)s->pend, (void *)s->snap_dev, (void *)s->srows, (void *)s->dlib, (void *)s->reset_mask,
+                    (void *)s->scene_built})
         (void)hipFree(p);
     for (StatePool *p : {&s->main, &s->shadow, &s->look.P, &s->fan.P}) pool_free(*p);
     delete s;

@@ -43,6 +43,7 @@ UNITS = {  # translation unit -> every header it includes, directly or not (one 
     "mg_seq_hbm.hip": _SEQ,
     "mg_raster.hip": _PHYS + ["mg_step.h", "mg_render.h"],
     "mg_replay.hip": _SIM,
+    "mg_scene.hip": _SIM + ["mg_math.h", "mg_phys.h", "mg_prof.h", "mg_reset.h", "mg_scene.h"],   # mg_get_scene, mg_reset_scene
 }
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 

@@ -101,7 +101,7 @@ class VecMagicalEnv:
     """Batched MAGICAL env on one MI355X (C ABI: include/magical_sim.h)."""
 
     def __init__(self, env_name, num_envs, device="cuda:0", seeds=None, base_seed=0, auto_reset=True,
-                 max_episode_steps=None, debug_reward=None, window=False):
+                 max_episode_steps=None, debug_reward=None, window=False, rand_flags=None):
         self.spec = registry.lookup(env_name)
         if not self.spec.gpu_supported:
             raise NotImplementedError(f"{env_name}: task not on the GPU hot path yet")
@@ -110,10 +110,13 @@ class VecMagicalEnv:
             # EagerDictFrameStack concatenates every observation value along the last axis; the
             # scalar target_type / target_colour make that raise in the reference as well
             raise ValueError(f"{env_name}: the reference cannot frame-stack PickAndPlace's scalar observations")
-        flags = self.spec.rand_flags
+        # rand_flags: a variant the registry has no name for (registry.LAYOUT_MINOR .. DYNAMICS bits) in place of the
+        # name's own, e.g. colour | shape type | dynamics with the Demo layout
+        flags = self.spec.rand_flags if rand_flags is None else int(rand_flags)
         if debug_reward is not None:  # gym.make(name, debug_reward=...)
             flags = (flags | registry.DEBUG_REWARD) if debug_reward else (flags & ~registry.DEBUG_REWARD)
         self.debug_reward = bool(flags & registry.DEBUG_REWARD)
+        self.rand_flags = flags
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.lib = native.load()
@@ -367,6 +370,56 @@ class VecMagicalEnv:
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
         native.check(self.lib.mg_get_errors(self.handle, ctypes.c_void_p(out.data_ptr()), self._stream()))
         return out
+
+    # -- explicit scenes ---------------------------------------------------------
+    def get_scenes(self, out=None):
+        """Every env's CURRENT layout as a structured array [N] of native.SCENE_DTYPE (mg_get_scene; scene.unpack turns
+        it into Scene objects): entity table, each entity's pose as it stands, goal geometry, physics variables,
+        PickAndPlace's target.  Read-only.  out: a contiguous uint8 device tensor of N * 792 bytes to fill instead, in
+        which case that tensor is returned and nothing is copied to the host."""
+        nbytes = self.num_envs * native.SCENE_DTYPE.itemsize
+        buf = out if out is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if buf.numel() != nbytes or buf.dtype != torch.uint8 or buf.device != self.device or not buf.is_contiguous():
+            raise ValueError(f"get_scenes: out must be a contiguous uint8 tensor of {nbytes} bytes on {self.device}")
+        native.check(self.lib.mg_get_scene(self.handle, ctypes.c_void_p(buf.data_ptr()), self._stream()))
+        if out is not None:
+            return out
+        return buf.cpu().numpy().view(native.SCENE_DTYPE).copy()
+
+    def _scene_tensor(self, scenes):
+        nbytes = self.num_envs * native.SCENE_DTYPE.itemsize
+        if isinstance(scenes, torch.Tensor):   # used in place
+            if (scenes.numel() != nbytes or scenes.dtype != torch.uint8 or scenes.device != self.device
+                    or not scenes.is_contiguous()):
+                raise ValueError(f"reset_scenes: a scene tensor must be contiguous uint8 of {nbytes} bytes on {self.device}")
+            return scenes
+        if not isinstance(scenes, np.ndarray):
+            from .scene import pack
+            scenes = pack(list(scenes))
+        arr = np.ascontiguousarray(scenes, dtype=native.SCENE_DTYPE).reshape(-1)
+        if arr.shape[0] != self.num_envs:
+            raise ValueError(f"reset_scenes: {arr.shape[0]} scenes for {self.num_envs} envs")
+        return torch.from_numpy(arr.view(np.uint8)).to(self.device)
+
+    def reset_scenes(self, scenes, mask=None, check=False):
+        """Start envs from given layouts (mg_reset_scene): a masked reset() whose layouts are `scenes` -- a structured
+        array [N] of native.SCENE_DTYPE, a list of N scene.Scene, or a uint8 device tensor of N * 792 bytes used in
+        place -- instead of the variant's draws.  Returns (obs, status): status i32[N] on the device, 0 built, -1 not
+        selected by `mask` (bool / uint8 [N]; None: every env), > 0 refused and left untouched (scene.STATUS_TEXT;
+        scene.validate gives the same code on the host).  check=True runs the reset's overlap test on the built envs:
+        one with overlapping entities gets error flags 2 | 64 (errors()), and is built all the same.  The envs' RNG
+        streams are not consumed: their next auto-reset draws what it would have drawn."""
+        t = self._scene_tensor(scenes)
+        m = None if mask is None else torch.as_tensor(mask).to(self.device, torch.uint8).contiguous()
+        status = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        self._last_scenes = (t, m)   # (alive until the next call: the kernel reads them on the stream)
+        native.check(self.lib.mg_reset_scene(self.handle, ctypes.c_void_p(t.data_ptr()),
+                                             None if m is None else ctypes.c_void_p(m.data_ptr()), 1 if check else 0,
+                                             ctypes.c_void_p(status.data_ptr()), self._stream()))
+        self.reset_count += 1
+        if self.spec.preproc is None:
+            self.render_full(out=self.full)
+        return self._obs(), status
 
     # -- snapshots ---------------------------------------------------------------
     def snapshot_bytes(self, n=None):
@@ -693,6 +746,25 @@ class MagicalEnv:
         obs = self._np_obs(self._vec.reset())
         if int(self._vec.errors()[0].item()) & 2:  # pm_randomise_all_poses raised (geom.py:335-336)
             raise PlacementError("could not place entities after 10 layout retries (geom.py:295-341)")
+        return obs
+
+    def get_scene(self):
+        """The current layout as a scene.Scene (VecMagicalEnv.get_scenes for this one env)."""
+        from .scene import unpack
+        return unpack(self._vec.get_scenes())[0]
+
+    def reset_scene(self, scene, check=False):
+        """reset() from a given layout (a scene.Scene): ValueError naming the status for a refused scene, which leaves
+        the env as it was; with check=True, PlacementError when entities overlap (the env is built all the same)."""
+        from .scene import STATUS_TEXT
+        obs, status = self._vec.reset_scenes([scene], check=check)
+        st = int(status[0].item())
+        if st != 0:
+            raise ValueError(f"reset_scene: status {st}: {STATUS_TEXT.get(st, 'unknown')}")
+        self._episode_steps = 0
+        obs = self._np_obs(obs)
+        if check and int(self._vec.errors()[0].item()) & 2:
+            raise PlacementError("reset_scene: entities of the scene overlap (status 0, error flags 2 | 64)")
         return obs
 
     def step(self, action):

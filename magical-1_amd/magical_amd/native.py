@@ -6,6 +6,8 @@ module raises at import time -- there is no CPU fallback.
 import ctypes
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmagical_sim_prof.so" if os.environ.get("MAGICAL_AMD_PROFILE") == "1"
                         else "libmagical_sim.so")
@@ -17,7 +19,7 @@ EXPORTS = ["mg_create", "mg_bind_outputs", "mg_reset", "mg_step", "mg_render_ful
            "mg_set_episode_steps", "mg_selftest_sincos", "mg_replay_lores", "mg_restack", "mg_restack_window", "mg_bind_window",
            "mg_window_start", "mg_snapshot_bytes", "mg_snapshot", "mg_restore", "mg_lookahead", "mg_plan", "mg_plan_sample",
            "mg_plan_cem", "mg_lookahead_obj", "mg_plan_obj", "mg_plan_cem_obj", "mg_plan_beam", "mg_step_seq", "mg_get_rng",
-           "mg_selftest_mt", "mg_destroy",
+           "mg_selftest_mt", "mg_get_scene", "mg_reset_scene", "mg_destroy",
            "mg_last_error"]
 PLAN_MAX_ROLLOUTS = 262144   # MG_PLAN_MAX_ROLLOUTS: K * num_envs of one mg_plan call
 OBJ_FINAL, OBJ_RETURN, OBJ_PEAK = 0, 1, 2   # MG_OBJ_*
@@ -67,6 +69,32 @@ class mg_plan_beam_out(ctypes.Structure):
     _fields_ = [("best", ctypes.c_void_p), ("best_value", ctypes.c_void_p), ("first_action", ctypes.c_void_p),
                 ("best_plan", ctypes.c_void_p), ("values", ctypes.c_void_p), ("steps", ctypes.c_void_p),
                 ("errors", ctypes.c_void_p), ("depth_values", ctypes.c_void_p), ("parents", ctypes.c_void_p)]
+
+
+SCENE_MAX_ENTS = 13   # MG_MAX_ENTS - 1: the entities of a scene after the arena
+
+
+class mg_scene_ent(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("type", ctypes.c_int32), ("colour", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("x", ctypes.c_double), ("y", ctypes.c_double), ("angle", ctypes.c_double),
+                ("h", ctypes.c_double), ("w", ctypes.c_double)]
+
+
+class mg_scene(ctypes.Structure):
+    _fields_ = [("n_ents", ctypes.c_int32), ("target_ent", ctypes.c_int32), ("pv", ctypes.c_double * 5),
+                ("target_xy", ctypes.c_double * 2), ("ent", mg_scene_ent * SCENE_MAX_ENTS)]
+
+
+# the same records as numpy structured arrays (little-endian, no padding: itemsize == sizeof(mg_scene))
+SCENE_ENT_DTYPE = np.dtype([("kind", "<i4"), ("type", "<i4"), ("colour", "<i4"), ("flags", "<i4"), ("x", "<f8"),
+                            ("y", "<f8"), ("angle", "<f8"), ("h", "<f8"), ("w", "<f8")])
+SCENE_DTYPE = np.dtype([("n_ents", "<i4"), ("target_ent", "<i4"), ("pv", "<f8", (5,)), ("target_xy", "<f8", (2,)),
+                        ("ent", SCENE_ENT_DTYPE, (SCENE_MAX_ENTS,))])
+# mg_reset_scene's per-env status codes
+SCENE_BUILT, SCENE_UNSELECTED, SCENE_BAD_ORDER, SCENE_BAD_RANGE, SCENE_NO_FIT, SCENE_BAD_TARGET = 0, -1, 1, 2, 3, 4
+SCENE_STATUS_TEXT = {0: "built", -1: "not selected", 1: "entity count or kind order is not the task's",
+                     2: "a field is out of range", 3: "the scene does not fit the handle's compiled slot caps",
+                     4: "PickAndPlace target_ent is not one of the blocks"}
 
 
 class NativeError(RuntimeError):
@@ -143,6 +171,9 @@ def load():
     lib.mg_plan_beam.argtypes = [vp, vp, vp, i32, i32, i32, i32, po, ctypes.POINTER(mg_plan_beam_out), vp]
     if hasattr(lib, "mg_step_seq"):   # (an experiment variant built from an older tree may predate it)
         lib.mg_step_seq.argtypes = [vp, vp, i32, vp, vp]
+    if hasattr(lib, "mg_get_scene"):   # (an experiment variant built from an older tree may predate them)
+        lib.mg_get_scene.argtypes = [vp, vp, vp]
+        lib.mg_reset_scene.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.mg_destroy.argtypes = [vp]
     lib.mg_destroy.restype = None
     lib.mg_last_error.restype = ctypes.c_char_p

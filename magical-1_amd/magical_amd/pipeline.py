@@ -152,6 +152,40 @@ class PipelinedVecEnv:
         self._fork()
         return self._obs()
 
+    def get_scenes(self):
+        """VecMagicalEnv.get_scenes for the whole pool: a structured array [num_envs] in env order."""
+        import numpy as np
+        self.wait()
+        return np.concatenate([sim.get_scenes() for sim in self.sims])
+
+    def reset_scenes(self, scenes, mask=None, check=False):
+        """VecMagicalEnv.reset_scenes for the whole pool, split per chunk as reset() is (on the caller's stream, once
+        every chunk's last step is done): `scenes` is a structured array [num_envs], a list of num_envs scene.Scene or a
+        uint8 device tensor of num_envs * 792 bytes; returns (obs, status i32[num_envs])."""
+        import numpy as np
+        from . import native
+        size, b = native.SCENE_DTYPE.itemsize, self.bounds
+        if not isinstance(scenes, (torch.Tensor, np.ndarray)):
+            from .scene import pack
+            scenes = pack(list(scenes))
+        if isinstance(scenes, np.ndarray):
+            scenes = torch.from_numpy(np.ascontiguousarray(scenes, dtype=native.SCENE_DTYPE).reshape(-1).view(np.uint8))
+        if scenes.numel() != self.num_envs * size or scenes.dtype != torch.uint8:
+            raise ValueError(f"reset_scenes: {self.num_envs} scenes of {size} bytes each")
+        scenes = scenes.reshape(-1).to(self.device).contiguous()
+        m = None if mask is None else torch.as_tensor(mask).to(self.device, torch.uint8)
+        self.wait()
+        status = [sim.reset_scenes(scenes[b[k] * size:b[k + 1] * size], None if m is None else m[b[k]:b[k + 1]],
+                                   check=check)[1] for k, sim in enumerate(self.sims)]
+        if self.target_f is not None:   # the resets ran on the caller's stream
+            self.target_f.copy_(self.target)
+            if self._target_out is not None:
+                self._target_out.copy_(self.target)
+        self.reset_count += 1
+        self._last = []
+        self._fork()
+        return self._obs(), torch.cat(status)
+
     def step(self, actions):
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.uint8 and a.device == self.device):
