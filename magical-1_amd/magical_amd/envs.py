@@ -97,6 +97,83 @@ def plan_actions(actions, num_envs):
     return a.to(torch.uint8)
 
 
+def _plan_fields(n, K, details, score="score"):
+    """(name, shape, dtype) of the results plan / plan_cem / plan_beam share: the three-entry head and, with details,
+    the [K, n] triple; the planners call the per-candidate number a score, the beam a value"""
+    head = [("best", (n,), torch.int32), ("best_" + score, (n,), torch.float64), ("first_action", (n,), torch.uint8)]
+    return head + ([(score + "s", (K, n), torch.float64), ("steps", (K, n), torch.int32),
+                    ("errors", (K, n), torch.int32)] if details else [])
+
+
+def seq_actions(actions, num_envs, fn, letter, device=None):
+    """step_seq()'s and lookahead()'s actions as a uint8 [X, num_envs] tensor ([num_envs] is X = 1) on `device` (None:
+    where they came from); ValueError, naming `fn` and the axis `letter`, for any other shape."""
+    a = torch.as_tensor(actions)
+    if a.dim() == 1:
+        a = a[None]
+    if a.dim() != 2 or a.shape[1] != num_envs:
+        raise ValueError(f"{fn}: actions must be [{letter}, {num_envs}], got {tuple(a.shape)}")
+    return a.to(device=device, dtype=torch.uint8)
+
+
+def check_out(out, fn, shape, device):
+    """An out= argument: `out` if it is a contiguous uint8 tensor on `device` of `shape` (an int: so many bytes in any
+    shape), else ValueError."""
+    flat = isinstance(shape, int)
+    if ((out.numel() != shape) if flat else (tuple(out.shape) != tuple(shape))) or out.dtype != torch.uint8 \
+            or out.device != device or not out.is_contiguous():
+        what = f"tensor of {shape} bytes" if flat else f"{list(shape)} tensor"
+        raise ValueError(f"{fn}: out must be a contiguous uint8 {what} on {device}")
+    return out
+
+
+def scene_tensor(scenes, num_envs, device, in_place=True):
+    """reset_scenes()'s `scenes` -- a list of scene.Scene, a structured array of native.SCENE_DTYPE or a uint8 tensor --
+    as a flat uint8 tensor of num_envs * 792 bytes on `device`.  in_place: a tensor must already be that and is
+    returned as it is (VecMagicalEnv); otherwise it is flattened and moved there (the pool, which slices it per chunk)."""
+    size = native.SCENE_DTYPE.itemsize
+    if isinstance(scenes, torch.Tensor):
+        ok = scenes.numel() == num_envs * size and scenes.dtype == torch.uint8
+        if not in_place:
+            if not ok:
+                raise ValueError(f"reset_scenes: {num_envs} scenes of {size} bytes each")
+            return scenes.reshape(-1).to(device).contiguous()
+        if not ok or scenes.device != device or not scenes.is_contiguous():
+            raise ValueError(f"reset_scenes: a scene tensor must be contiguous uint8 of {num_envs * size} bytes on {device}")
+        return scenes
+    if not isinstance(scenes, np.ndarray):
+        from .scene import pack
+        scenes = pack(list(scenes))
+    arr = np.ascontiguousarray(scenes, dtype=native.SCENE_DTYPE).reshape(-1)
+    if arr.shape[0] != num_envs:
+        raise ValueError(f"reset_scenes: {arr.shape[0]} scenes for {num_envs} envs" if in_place
+                         else f"reset_scenes: {num_envs} scenes of {size} bytes each")
+    return torch.from_numpy(arr.view(np.uint8)).to(device)
+
+
+def assemble_obs(allo, ego, past, rings, s0, chw, target):
+    """The observation dict both env classes return, from the raw HWC buffers.  rings: None, or the (allo, ego) window
+    rings whose stacks at first slot s0 stand in for buffers -- two rings (LoResStack) are the allo and ego stacks
+    themselves, one is past_obs.  chw: the image keys become CHW views.  target: PickAndPlace's [n, 4] float32 target
+    (SB3's DummyVecEnv buffers it as float32, per the spaces) or None.  Key order: allo, ego, target keys, past_obs."""
+    if rings is not None:
+        stacks = [None if r is None else window_stack(r, s0, r.shape[1] - 3) for r in rings]
+        if stacks[0] is not None and stacks[1] is not None:
+            allo, ego = stacks
+        else:
+            past = stacks[0] if stacks[0] is not None else stacks[1]
+    out = collections.OrderedDict([("allo", allo), ("ego", ego)])
+    if target is not None:
+        out["target_type"], out["target_colour"], out["target_position"] = target[:, 0:1], target[:, 1:2], target[:, 2:4]
+    if past is not None:
+        out["past_obs"] = past
+    if chw:
+        for k in ("allo", "ego", "past_obs"):
+            if k in out:
+                out[k] = out[k].permute(0, 3, 1, 2)
+    return out
+
+
 class VecMagicalEnv:
     """Batched MAGICAL env on one MI355X (C ABI: include/magical_sim.h)."""
 
@@ -236,25 +313,24 @@ class VecMagicalEnv:
 
     def _obs(self):
         if self.spec.preproc is None:
-            out = collections.OrderedDict([("allo", self.full[:, 0]), ("ego", self.full[:, 1])])
-            past = None
+            allo, ego, past = self.full[:, 0], self.full[:, 1], None
         else:
             allo, ego, past = self.obs_allo, self.obs_ego, self.obs_past
-            if self.window_k and not self.frames_only:
-                s0 = self.window_start()
-                if self.spec.preproc == "LoResStack":
-                    allo, ego = window_stack(self.wring[0], s0, self.window_k), window_stack(self.wring[1], s0, self.window_k)
-                else:
-                    past = window_stack(self.wring[0] if self.wring[0] is not None else self.wring[1], s0, self.window_k)
-            out = collections.OrderedDict([("allo", allo), ("ego", ego)])
-            if self._chw:
-                out = collections.OrderedDict((k, v.permute(0, 3, 1, 2)) for k, v in out.items())
-        if self.target is not None:  # as SB3's DummyVecEnv buffers them: float32 per the spaces
-            t = self.target.to(torch.float32)
-            out["target_type"], out["target_colour"], out["target_position"] = t[:, 0:1], t[:, 1:2], t[:, 2:4]
-        if past is not None:
-            out["past_obs"] = past.permute(0, 3, 1, 2) if self._chw else past
-        return out
+        windowed = self.window_k and not self.frames_only
+        return assemble_obs(allo, ego, past, self.wring if windowed else None, self.window_start() if windowed else 0,
+                            self._chw, None if self.target is None else self.target.to(torch.float32))
+
+    def _finish(self):
+        """the tail of every call that changes what the envs show: the observation, the unwrapped view rendered first"""
+        if self.spec.preproc is None:
+            self.render_full(out=self.full)
+        return self._obs()
+
+    def _alloc(self, fields, zeros=()):
+        """fresh result tensors on the device from (name, shape, dtype) triples, uninitialised but for `zeros`"""
+        return collections.OrderedDict(
+            (name, (torch.zeros if name in zeros else torch.empty)(shape, dtype=dtype, device=self.device))
+            for name, shape, dtype in fields)
 
     # -- API -----------------------------------------------------------------
     def seed(self, seeds):
@@ -266,9 +342,7 @@ class VecMagicalEnv:
         m = None if mask is None else ctypes.c_void_p(mask.to(self.device, torch.uint8).contiguous().data_ptr())
         native.check(self.lib.mg_reset(self.handle, m, self._stream()))
         self.reset_count += 1
-        if self.spec.preproc is None:
-            self.render_full(out=self.full)
-        return self._obs()
+        return self._finish()
 
     def step(self, actions):
         a = actions
@@ -276,9 +350,7 @@ class VecMagicalEnv:
             a = torch.as_tensor(actions).to(self.device, torch.uint8).contiguous()
         self._last_actions = a
         native.check(self.lib.mg_step(self.handle, ctypes.c_void_p(a.data_ptr()), self._stream()))
-        if self.spec.preproc is None:
-            self.render_full(out=self.full)
-        return self._obs(), self.reward, self.done, {"eval_score": self.eval_score}
+        return self._finish(), self.reward, self.done, {"eval_score": self.eval_score}
 
     def step_seq(self, actions):
         """Several env-steps per call with one render (frame skip; mg_step_seq).  actions: [R, N] uint8 (tensor or
@@ -288,21 +360,13 @@ class VecMagicalEnv:
         boundaries.  Returns (obs, reward, done, info): reward is the float32 of the n rewards summed in double, done
         says whether step n ended the episode, info holds 'eval_score' (the score at that step, else 0) and 'steps'
         i32[N] (n).  step_seq(a[None]) is step(a)."""
-        a = torch.as_tensor(actions)
-        if a.dim() == 1:
-            a = a[None]
-        if a.dim() != 2 or a.shape[1] != self.num_envs:
-            raise ValueError(f"step_seq: actions must be [R, {self.num_envs}], got {tuple(a.shape)}")
-        if not (a.dtype == torch.uint8 and a.device == self.device and a.is_contiguous()):
-            a = a.to(self.device, torch.uint8).contiguous()
+        a = seq_actions(actions, self.num_envs, "step_seq", "R", self.device).contiguous()
         self._last_actions = a   # (alive until the next call: the kernel reads it on the stream)
         if self.seq_steps is None:   # (no fill: the kernel writes every env's element)
             self.seq_steps = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
         native.check(self.lib.mg_step_seq(self.handle, ctypes.c_void_p(a.data_ptr()), int(a.shape[0]),
                                           ctypes.c_void_p(self.seq_steps.data_ptr()), self._stream()))
-        if self.spec.preproc is None:
-            self.render_full(out=self.full)
-        return self._obs(), self.reward, self.done, {"eval_score": self.eval_score, "steps": self.seq_steps}
+        return self._finish(), self.reward, self.done, {"eval_score": self.eval_score, "steps": self.seq_steps}
 
     def step_repeat(self, actions, repeat):
         """step_seq with every env's action held for `repeat` env-steps (action repeat).  actions: [N] uint8."""
@@ -378,28 +442,15 @@ class VecMagicalEnv:
         PickAndPlace's target.  Read-only.  out: a contiguous uint8 device tensor of N * 792 bytes to fill instead, in
         which case that tensor is returned and nothing is copied to the host."""
         nbytes = self.num_envs * native.SCENE_DTYPE.itemsize
-        buf = out if out is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        if buf.numel() != nbytes or buf.dtype != torch.uint8 or buf.device != self.device or not buf.is_contiguous():
-            raise ValueError(f"get_scenes: out must be a contiguous uint8 tensor of {nbytes} bytes on {self.device}")
+        buf = (torch.empty(nbytes, dtype=torch.uint8, device=self.device) if out is None
+               else check_out(out, "get_scenes", nbytes, self.device))
         native.check(self.lib.mg_get_scene(self.handle, ctypes.c_void_p(buf.data_ptr()), self._stream()))
         if out is not None:
             return out
         return buf.cpu().numpy().view(native.SCENE_DTYPE).copy()
 
     def _scene_tensor(self, scenes):
-        nbytes = self.num_envs * native.SCENE_DTYPE.itemsize
-        if isinstance(scenes, torch.Tensor):   # used in place
-            if (scenes.numel() != nbytes or scenes.dtype != torch.uint8 or scenes.device != self.device
-                    or not scenes.is_contiguous()):
-                raise ValueError(f"reset_scenes: a scene tensor must be contiguous uint8 of {nbytes} bytes on {self.device}")
-            return scenes
-        if not isinstance(scenes, np.ndarray):
-            from .scene import pack
-            scenes = pack(list(scenes))
-        arr = np.ascontiguousarray(scenes, dtype=native.SCENE_DTYPE).reshape(-1)
-        if arr.shape[0] != self.num_envs:
-            raise ValueError(f"reset_scenes: {arr.shape[0]} scenes for {self.num_envs} envs")
-        return torch.from_numpy(arr.view(np.uint8)).to(self.device)
+        return scene_tensor(scenes, self.num_envs, self.device)
 
     def reset_scenes(self, scenes, mask=None, check=False):
         """Start envs from given layouts (mg_reset_scene): a masked reset() whose layouts are `scenes` -- a structured
@@ -417,9 +468,7 @@ class VecMagicalEnv:
                                              None if m is None else ctypes.c_void_p(m.data_ptr()), 1 if check else 0,
                                              ctypes.c_void_p(status.data_ptr()), self._stream()))
         self.reset_count += 1
-        if self.spec.preproc is None:
-            self.render_full(out=self.full)
-        return self._obs(), status
+        return self._finish(), status
 
     # -- snapshots ---------------------------------------------------------------
     def snapshot_bytes(self, n=None):
@@ -441,9 +490,8 @@ class VecMagicalEnv:
         from .snapshot import Snapshot
         n = self.num_envs if envs is None else len(envs)
         nbytes = self.snapshot_bytes(n)
-        blob = out if out is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        if blob.numel() != nbytes or blob.dtype != torch.uint8 or blob.device != self.device or not blob.is_contiguous():
-            raise ValueError(f"snapshot: out must be a contiguous uint8 tensor of {nbytes} bytes on {self.device}")
+        blob = (torch.empty(nbytes, dtype=torch.uint8, device=self.device) if out is None
+                else check_out(out, "snapshot", nbytes, self.device))
         arr = None if envs is None else (ctypes.c_int32 * n)(*[int(e) for e in envs])
         native.check(self.lib.mg_snapshot(self.handle, arr, n, ctypes.c_void_p(blob.data_ptr()), self._stream()))
         return Snapshot(blob, count=n)
@@ -464,9 +512,7 @@ class VecMagicalEnv:
                 self._restore(chunk, range(snap.bounds[k], snap.bounds[k + 1]), None)
         else:
             self._restore(snap, envs, recs)
-        if self.spec.preproc is None:
-            self.render_full(out=self.full)
-        return self._obs()
+        return self._finish()
 
     def _restore(self, snap, envs, recs):
         if snap.device != self.device:
@@ -501,33 +547,19 @@ class VecMagicalEnv:
         score after step h + 1, held at the final score past the env's last step) and 'reward_trace' f64[H, N] (the
         reward step() would pay at step h + 1 before its cast to float32, 0 past the env's last step); without an
         objective the traces are those of Objective('final').  With neither, nothing changes."""
-        a = torch.as_tensor(actions)
-        if a.dim() == 1:
-            a = a[None]
-        if a.dim() != 2 or a.shape[1] != self.num_envs:
-            raise ValueError(f"lookahead: actions must be [H, {self.num_envs}], got {tuple(a.shape)}")
-        a = a.to(self.device, torch.uint8).contiguous()
-        n, dev = self.num_envs, self.device
-        res = collections.OrderedDict([("score", torch.empty(n, dtype=torch.float64, device=dev)),
-                                       ("steps", torch.empty(n, dtype=torch.int32, device=dev)),
-                                       ("errors", torch.empty(n, dtype=torch.int32, device=dev))])
-        if bodies:
-            res["bodies"] = torch.empty((n, 16, 6), dtype=torch.float64, device=dev)
-            res["counts"] = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        a = seq_actions(actions, self.num_envs, "lookahead", "H", self.device).contiguous()
+        n, f64, i32 = self.num_envs, torch.float64, torch.int32
+        res = self._alloc([("score", (n,), f64), ("steps", (n,), i32), ("errors", (n,), i32)]
+                          + ([("bodies", (n, 16, 6), f64), ("counts", (n, 4), i32)] if bodies else []))
         out = native.mg_lookahead_out(**{k: v.data_ptr() for k, v in res.items()})
         ap, H = ctypes.c_void_p(a.data_ptr()) if a.shape[0] else None, int(a.shape[0])
         if objective is None and not trace:
             native.check(self.lib.mg_lookahead(self.handle, ap, H, ctypes.byref(out), self._stream()))
         else:
             obj = self._objective_struct("final" if objective is None else objective, "lookahead")
-            extra = collections.OrderedDict()
-            if objective is not None:
-                extra["value"] = torch.empty(n, dtype=torch.float64, device=dev)
-                extra["peak"] = torch.empty(n, dtype=torch.float64, device=dev)
-                extra["peak_step"] = torch.empty(n, dtype=torch.int32, device=dev)
-            if trace:
-                extra["score_trace"] = torch.empty((H, n), dtype=torch.float64, device=dev)
-                extra["reward_trace"] = torch.empty((H, n), dtype=torch.float64, device=dev)
+            extra = self._alloc(
+                ([("value", (n,), f64), ("peak", (n,), f64), ("peak_step", (n,), i32)] if objective is not None else [])
+                + ([("score_trace", (H, n), f64), ("reward_trace", (H, n), f64)] if trace else []))
             oo = native.mg_objective_out(**{k: v.data_ptr() for k, v in extra.items() if v.numel()})
             native.check(self.lib.mg_lookahead_obj(self.handle, ap, H, ctypes.byref(obj), ctypes.byref(out),
                                                    ctypes.byref(oo), self._stream()))
@@ -554,14 +586,8 @@ class VecMagicalEnv:
         objective (a magical_amd.Objective; mg_plan_obj): 'scores' and 'best_score' hold the objective's value --
         lookahead(actions[:, k], objective=objective)['value'] -- and 'best' is chosen on it."""
         a = plan_actions(actions, self.num_envs).to(self.device).contiguous()
-        H, K, n, dev = int(a.shape[0]), int(a.shape[1]), self.num_envs, self.device
-        res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
-                                       ("best_score", torch.empty(n, dtype=torch.float64, device=dev)),
-                                       ("first_action", torch.zeros(n, dtype=torch.uint8, device=dev))])
-        if details:
-            res["scores"] = torch.empty((K, n), dtype=torch.float64, device=dev)
-            res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
-            res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+        H, K = int(a.shape[0]), int(a.shape[1])
+        res = self._alloc(_plan_fields(self.num_envs, K, details), zeros=("first_action",))   # (zeros: H = 0 writes none)
         out = native.mg_plan_out(**{k: v.data_ptr() for k, v in res.items()})
         ap = ctypes.c_void_p(a.data_ptr()) if H else None
         if objective is None:
@@ -578,9 +604,7 @@ class VecMagicalEnv:
         H, K = int(H), int(K)
         if out is None:
             out = torch.empty((max(H, 0), max(K, 0), self.num_envs), dtype=torch.uint8, device=self.device)
-        if (tuple(out.shape) != (H, K, self.num_envs) or out.dtype != torch.uint8 or out.device != self.device
-                or not out.is_contiguous()):
-            raise ValueError(f"sample_plans: out must be a contiguous uint8 [{H}, {K}, {self.num_envs}] tensor on {self.device}")
+        check_out(out, "sample_plans", (H, K, self.num_envs), self.device)   # (a negative H or K fails here, too)
         # (H = 0: the call checks K and repeat and writes nothing, but refuses a null pointer)
         buf = out if out.numel() else torch.empty(1, dtype=torch.uint8, device=self.device)
         native.check(self.lib.mg_plan_sample(self.handle, ctypes.c_void_p(buf.data_ptr()), H, K, int(repeat), int(key),
@@ -615,14 +639,7 @@ class VecMagicalEnv:
                 or weights.device != dev or not weights.is_contiguous()):
             raise ValueError(f"plan_cem: weights must be a contiguous uint16 [{J}, 18, {n}] tensor on {dev}")
         acts = torch.empty((H, K, n), dtype=torch.uint8, device=dev)
-        res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
-                                       ("best_score", torch.empty(n, dtype=torch.float64, device=dev)),
-                                       ("first_action", torch.empty(n, dtype=torch.uint8, device=dev)),
-                                       ("iter_best", torch.empty((iters, n), dtype=torch.float64, device=dev))])
-        if details:
-            res["scores"] = torch.empty((K, n), dtype=torch.float64, device=dev)
-            res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
-            res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
+        res = self._alloc(_plan_fields(n, K, details) + [("iter_best", (iters, n), torch.float64)])
         out = native.mg_plan_cem_out(**{k: v.data_ptr() for k, v in res.items()})
         args = (self.handle, ctypes.c_void_p(acts.data_ptr()), ctypes.c_void_p(weights.data_ptr()), int(warm), H, K, iters,
                 int(elites), int(alpha), repeat, int(key), int(step))
@@ -665,16 +682,9 @@ class VecMagicalEnv:
         a = a.to(dev).contiguous()
         D = -(-H // seg)
         plans = torch.empty((H, K, n), dtype=torch.uint8, device=dev)
-        res = collections.OrderedDict([("best", torch.empty(n, dtype=torch.int32, device=dev)),
-                                       ("best_value", torch.empty(n, dtype=torch.float64, device=dev)),
-                                       ("first_action", torch.empty(n, dtype=torch.uint8, device=dev)),
-                                       ("best_plan", torch.empty((H, n), dtype=torch.uint8, device=dev))])
-        if details:
-            res["values"] = torch.empty((K, n), dtype=torch.float64, device=dev)
-            res["steps"] = torch.empty((K, n), dtype=torch.int32, device=dev)
-            res["errors"] = torch.empty((K, n), dtype=torch.int32, device=dev)
-            res["depth_values"] = torch.empty((D, K, n), dtype=torch.float64, device=dev)
-            res["parents"] = torch.empty((D - 1, K, n), dtype=torch.int32, device=dev)
+        res = self._alloc(_plan_fields(n, K, details, "value") + [("best_plan", (H, n), torch.uint8)]
+                          + ([("depth_values", (D, K, n), torch.float64), ("parents", (D - 1, K, n), torch.int32)]
+                             if details else []))
         out = native.mg_plan_beam_out(**{k: v.data_ptr() for k, v in res.items() if v.numel()})
         native.check(self.lib.mg_plan_beam(self.handle, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(plans.data_ptr()),
                                            H, K, seg, survivors, None if obj is None else ctypes.byref(obj),
@@ -731,6 +741,18 @@ class MagicalEnv:
     def flags_to_action(self, flags):
         return FLAGS_TO_ACTION_ID[tuple(flags)]
 
+    def _require_reset(self, fn):
+        if self._episode_steps is None:
+            raise RuntimeError(f"call reset() before {fn}()")
+
+    @staticmethod
+    def _candidates(actions, fn):
+        """[H, K] action ids as the one-env vec env's uint8 [H, K, 1]"""
+        a = torch.as_tensor(np.asarray(actions), dtype=torch.uint8)
+        if a.dim() != 2:
+            raise ValueError(f"{fn}: actions must be [H, K], got {tuple(a.shape)}")
+        return a[:, :, None]
+
     def _np_obs(self, obs):
         out = collections.OrderedDict()
         for k, v in obs.items():
@@ -768,8 +790,7 @@ class MagicalEnv:
         return obs
 
     def step(self, action):
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before step()")
+        self._require_reset("step")
         obs, rew, done, info = self._vec.step(torch.tensor([int(action)], dtype=torch.uint8))
         self._episode_steps += 1
         d = bool(done[0].item())
@@ -780,8 +801,7 @@ class MagicalEnv:
         """Run `actions` (a sequence of 1 .. 4096 action ids) as env-steps, stopping at the episode's end, and render
         once: (obs, summed reward, done, {'eval_score', 'steps': env-steps run}) -- VecMagicalEnv.step_seq for this
         one env."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before step_seq()")
+        self._require_reset("step_seq")
         a = torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1)
         obs, rew, done, info = self._vec.step_seq(a)
         n = int(info["steps"][0].item())
@@ -792,8 +812,7 @@ class MagicalEnv:
     def score(self):
         """The task's score (score_on_end_of_traj) of the current state, at any point of the episode; step() reports
         it as info['eval_score'] only on the step that ends one."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before score()")
+        self._require_reset("score")
         return float(self._vec.score()[0].item())
 
     def lookahead(self, actions, objective=None, trace=False):
@@ -802,14 +821,12 @@ class MagicalEnv:
         magical_amd.Objective) or trace=True the result is a dict instead: 'score' and 'steps' as above, with an
         objective 'value', 'peak' (floats) and 'peak_step' (int), with trace=True 'score_trace' and 'reward_trace'
         as float64 arrays [H] (VecMagicalEnv.lookahead for this one env)."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before lookahead()")
+        self._require_reset("lookahead")
         a = torch.as_tensor(list(actions), dtype=torch.uint8).reshape(-1, 1)
-        if objective is None and not trace:
-            res = self._vec.lookahead(a)
-            return float(res["score"][0].item()), int(res["steps"][0].item())
         res = self._vec.lookahead(a, objective=objective, trace=trace)
         out = {"score": float(res["score"][0].item()), "steps": int(res["steps"][0].item())}
+        if objective is None and not trace:
+            return out["score"], out["steps"]
         if objective is not None:
             out.update(value=float(res["value"][0].item()), peak=float(res["peak"][0].item()),
                        peak_step=int(res["peak_step"][0].item()))
@@ -822,13 +839,9 @@ class MagicalEnv:
         action ids (candidate k is the column actions[:, k]).  Returns (best, best_score, scores): the index of the
         highest-scoring candidate (the lowest on ties), its score, and every candidate's score as a float64 array [K].
         With an objective (a magical_amd.Objective) the scores are its values and the best is chosen on them."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before plan()")
-        a = torch.as_tensor(np.asarray(actions), dtype=torch.uint8)
-        if a.dim() != 2:
-            raise ValueError(f"plan: actions must be [H, K], got {tuple(a.shape)}")
-        kw = {} if objective is None else {"objective": objective}
-        res = self._vec.plan(a[:, :, None], details=True, **kw)
+        self._require_reset("plan")
+        a = self._candidates(actions, "plan")
+        res = self._vec.plan(a, details=True, objective=objective)
         return int(res["best"][0].item()), float(res["best_score"][0].item()), res["scores"][:, 0].cpu().numpy()
 
     def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, objective=None):
@@ -836,30 +849,24 @@ class MagicalEnv:
         env, from uniform weights).  Returns (plan, best_score, iter_best): the best action sequence found as a
         uint8 array [H], its score, and the best score of every iteration as a float64 array [iters].  With an
         objective (a magical_amd.Objective) the scores are its values."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before plan_cem()")
-        kw = {} if objective is None else {"objective": objective}
-        res = self._vec.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key, step=step, **kw)
+        self._require_reset("plan_cem")
+        res = self._vec.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key, step=step,
+                                 objective=objective)
         return res["plan"][:, 0].cpu().numpy(), float(res["best_score"][0].item()), res["iter_best"][:, 0].cpu().numpy()
 
     def plan_beam(self, actions, seg, survivors, objective=None):
         """Beam search over action segments from the current state, which stays as it is (VecMagicalEnv.plan_beam for
         this one env).  actions: [H, K] action ids.  Returns (plan, best_value, values): the best lineage's actions as a
         uint8 array [H], its value, and every slot's value after the last segment as a float64 array [K]."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before plan_beam()")
-        a = torch.as_tensor(np.asarray(actions), dtype=torch.uint8)
-        if a.dim() != 2:
-            raise ValueError(f"plan_beam: actions must be [H, K], got {tuple(a.shape)}")
-        kw = {} if objective is None else {"objective": objective}
-        res = self._vec.plan_beam(a[:, :, None], seg, survivors, details=True, **kw)
+        self._require_reset("plan_beam")
+        a = self._candidates(actions, "plan_beam")
+        res = self._vec.plan_beam(a, seg, survivors, details=True, objective=objective)
         return res["plan"][:, 0].cpu().numpy(), float(res["best_value"][0].item()), res["values"][:, 0].cpu().numpy()
 
     def get_state(self):
         """The env's whole state as bytes (a one-record snapshot blob, magical_amd.snapshot): physics, RNG, episode
         phase and frame stacks.  Host-side wrapper statistics (e.g. an SB3 Monitor around this env) are not in it."""
-        if self._episode_steps is None:
-            raise RuntimeError("call reset() before get_state()")
+        self._require_reset("get_state")
         return self._vec.snapshot().tobytes()
 
     def set_state(self, state):

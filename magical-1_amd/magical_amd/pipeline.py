@@ -24,7 +24,33 @@ import ctypes
 import torch
 
 from . import native
-from .envs import VecMagicalEnv
+from .envs import VecMagicalEnv, assemble_obs, plan_actions, scene_tensor, seq_actions
+
+
+_SIGNED = {torch.uint16: torch.int16, torch.uint32: torch.int32}
+
+
+def cat_bits(tensors, dim=0):
+    """torch.cat that also takes uint16 and uint32, for which it has no kernel: they are joined as their signed twins,
+    the same bytes"""
+    signed = _SIGNED.get(tensors[0].dtype)
+    if signed is None:
+        return torch.cat(tensors, dim=dim)
+    return torch.cat([t.view(signed) for t in tensors], dim=dim).view(tensors[0].dtype)
+
+
+def join(parts, stream=None):
+    """The chunks' result dicts as one, every key concatenated in env order: envs are the first axis of 'bodies' and
+    'counts' and the last axis of every other result ([n], [K, n], [H, n], [H, K, n], [J, 18, n]).  stream: the stream
+    that reads the parts here, where they were allocated on the chunks' own."""
+    out = collections.OrderedDict()
+    for key in parts[0]:
+        tensors = [p[key] for p in parts]
+        out[key] = cat_bits(tensors, dim=0 if key in ("bodies", "counts") else -1)
+        if stream is not None:
+            for t in tensors:
+                t.record_stream(stream)
+    return out
 
 
 # tasks measured faster pipelined (round 4): their scenes run the compile-time robot forms of the step
@@ -120,6 +146,41 @@ class PipelinedVecEnv:
             ev.record(self.streams[k])
             cs.wait_event(ev)
 
+    def _per_chunk(self, fn, pre_wait=True, post_wait=True):
+        """[fn(k, sim, lo, hi) for every chunk k], each called under the chunk's stream, whose envs are [lo, hi).
+        pre_wait: every chunk's earlier work is done before any chunk starts; post_wait: the caller's stream is
+        ordered after what fn enqueued."""
+        if pre_wait:
+            self.wait()
+        self._fork()
+        out = []
+        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
+            with torch.cuda.stream(st):
+                out.append(fn(k, sim, self.bounds[k], self.bounds[k + 1]))
+        if post_wait:
+            self.wait()
+        return out
+
+    def _publish_target(self, k=None):
+        """PickAndPlace: copy the persistent float64 target into the observation's float32 columns and into
+        bind_outputs' "target" view, on the current stream -- chunk k's rows right after a call that may have reset its
+        envs (a conversion on the caller's stream would read the target before the chunk wrote it), every row when
+        k is None."""
+        if self.target_f is None:
+            return
+        rows = slice(None) if k is None else slice(self.bounds[k], self.bounds[k + 1])
+        self.target_f[rows].copy_(self.target[rows])
+        if self._target_out is not None:
+            self._target_out[rows].copy_(self.target[rows])
+
+    def _after_reset(self):
+        """the tail of reset() and reset_scenes(), whose per-chunk resets ran on the caller's stream"""
+        self._publish_target()
+        self.reset_count += 1
+        self._last = []
+        self._fork()
+        return self._obs()
+
     def step_events(self):
         """Events recorded on every chunk's stream after its last step() (a consumer on another stream, e.g.
         magical_amd.dist's collective, waits on them instead of ordering the caller's stream after the chunks,
@@ -143,14 +204,7 @@ class PipelinedVecEnv:
         self.wait()
         for k, sim in enumerate(self.sims):
             sim.reset(None if mask is None else mask[self.bounds[k]:self.bounds[k + 1]])
-        if self.target_f is not None:   # the resets ran on the caller's stream
-            self.target_f.copy_(self.target)
-            if self._target_out is not None:
-                self._target_out.copy_(self.target)
-        self.reset_count += 1
-        self._last = []
-        self._fork()
-        return self._obs()
+        return self._after_reset()
 
     def get_scenes(self):
         """VecMagicalEnv.get_scenes for the whole pool: a structured array [num_envs] in env order."""
@@ -162,31 +216,16 @@ class PipelinedVecEnv:
         """VecMagicalEnv.reset_scenes for the whole pool, split per chunk as reset() is (on the caller's stream, once
         every chunk's last step is done): `scenes` is a structured array [num_envs], a list of num_envs scene.Scene or a
         uint8 device tensor of num_envs * 792 bytes; returns (obs, status i32[num_envs])."""
-        import numpy as np
-        from . import native
         size, b = native.SCENE_DTYPE.itemsize, self.bounds
-        if not isinstance(scenes, (torch.Tensor, np.ndarray)):
-            from .scene import pack
-            scenes = pack(list(scenes))
-        if isinstance(scenes, np.ndarray):
-            scenes = torch.from_numpy(np.ascontiguousarray(scenes, dtype=native.SCENE_DTYPE).reshape(-1).view(np.uint8))
-        if scenes.numel() != self.num_envs * size or scenes.dtype != torch.uint8:
-            raise ValueError(f"reset_scenes: {self.num_envs} scenes of {size} bytes each")
-        scenes = scenes.reshape(-1).to(self.device).contiguous()
+        scenes = scene_tensor(scenes, self.num_envs, self.device, in_place=False)
         m = None if mask is None else torch.as_tensor(mask).to(self.device, torch.uint8)
         self.wait()
         status = [sim.reset_scenes(scenes[b[k] * size:b[k + 1] * size], None if m is None else m[b[k]:b[k + 1]],
                                    check=check)[1] for k, sim in enumerate(self.sims)]
-        if self.target_f is not None:   # the resets ran on the caller's stream
-            self.target_f.copy_(self.target)
-            if self._target_out is not None:
-                self._target_out.copy_(self.target)
-        self.reset_count += 1
-        self._last = []
-        self._fork()
-        return self._obs(), torch.cat(status)
+        return self._after_reset(), torch.cat(status)
 
     def step(self, actions):
+        # (the benchmarked path: its own loop, not _per_chunk, whose closure and result list it does not need)
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.uint8 and a.device == self.device):
             a = torch.as_tensor(actions).to(self.device, torch.uint8)
@@ -201,10 +240,7 @@ class PipelinedVecEnv:
         for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
             with torch.cuda.stream(st):
                 sim.step(self.abuf[slot, b[k]:b[k + 1]])
-                if self.target_f is not None:
-                    self.target_f[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
-                    if self._target_out is not None:
-                        self._target_out[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
+                self._publish_target(k)
             ev = torch.cuda.Event()
             ev.record(st)
             self.done_ev[k][slot] = ev
@@ -217,32 +253,23 @@ class PipelinedVecEnv:
         columns [bounds[k], bounds[k + 1]) as one mg_step_seq call on its own stream, as step() does, and like step()
         the call only enqueues: a chunk's outputs are complete after wait(k) / wait().  info holds 'eval_score' and
         'steps' i32[num_envs]."""
-        a = torch.as_tensor(actions)
-        if a.dim() == 1:
-            a = a[None]
-        if a.dim() != 2 or a.shape[1] != self.num_envs:
-            raise ValueError(f"step_seq: actions must be [R, {self.num_envs}], got {tuple(a.shape)}")
-        a = a.to(self.device, torch.uint8)
+        a = seq_actions(actions, self.num_envs, "step_seq", "R", self.device)
         b = self.bounds
         if self.seq_steps is None:   # the chunks' info['steps'] as slices of one pool tensor
             self.seq_steps = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
             for k, sim in enumerate(self.sims):
                 sim.seq_steps = self.seq_steps[b[k]:b[k + 1]]
-        # a column slice is strided: every chunk gets its own contiguous [R, m] copy, made on the caller's stream
+        # a column slice is strided: every chunk gets its own contiguous [R, m] copy.  As step() copies the actions
+        # into abuf, they are made on the caller's stream before the fork, so they run beside the chunks' unfinished
+        # work (this call does not wait() for it); the planning calls, which do, make theirs on the chunks' streams
         parts = [a[:, b[k]:b[k + 1]].contiguous() for k in range(self.chunks)]
-        self._fork()
-        self._last = []
-        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
-            parts[k].record_stream(st)
-            with torch.cuda.stream(st):
-                sim.step_seq(parts[k])
-                if self.target_f is not None:
-                    self.target_f[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
-                    if self._target_out is not None:
-                        self._target_out[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
-            ev = torch.cuda.Event()
-            ev.record(st)
-            self._last.append(ev)
+
+        def run(k, sim, lo, hi):
+            parts[k].record_stream(self.streams[k])
+            sim.step_seq(parts[k])
+            self._publish_target(k)
+            return self.streams[k].record_event()
+        self._last = self._per_chunk(run, pre_wait=False, post_wait=False)
         return self._obs(), self.buffers["reward"], self.buffers["done"], \
             {"eval_score": self.buffers["eval_score"], "steps": self.seq_steps}
 
@@ -252,15 +279,8 @@ class PipelinedVecEnv:
         restores into a pool with the same chunking, or into a plain VecMagicalEnv of the same envs in the same
         order (VecMagicalEnv.restore).  Materialised stacks only (not window=True)."""
         from .snapshot import PoolSnapshot
-        self.wait()
         blobs = [torch.empty(sim.snapshot_bytes(), dtype=torch.uint8, device=self.device) for sim in self.sims]
-        self._fork()
-        snaps = []
-        for sim, st, blob in zip(self.sims, self.streams, blobs):
-            with torch.cuda.stream(st):
-                snaps.append(sim.snapshot(out=blob))
-        self.wait()
-        return PoolSnapshot(snaps, self.bounds)
+        return PoolSnapshot(self._per_chunk(lambda k, sim, lo, hi: sim.snapshot(out=blobs[k])), self.bounds)
 
     def restore(self, snap):
         """Put every env of the pool back to a PoolSnapshot of the same chunking, each chunk on its own stream, and
@@ -269,87 +289,36 @@ class PipelinedVecEnv:
         if not isinstance(snap, PoolSnapshot) or snap.bounds != self.bounds:
             raise ValueError(f"PipelinedVecEnv.restore: a PoolSnapshot with chunk bounds {self.bounds}")
         snap = snap.to(self.device)
-        self.wait()
-        self._fork()
-        b = self.bounds
-        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
-            with torch.cuda.stream(st):
-                sim.restore(snap.chunks[k])
-                if self.target_f is not None:
-                    self.target_f[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
-                    if self._target_out is not None:
-                        self._target_out[b[k]:b[k + 1]].copy_(self.target[b[k]:b[k + 1]])
-        self.wait()
+
+        def run(k, sim, lo, hi):
+            sim.restore(snap.chunks[k])
+            self._publish_target(k)
+        self._per_chunk(run)
         self._last = []
         return self._obs()
 
+    # The planning calls: chunk k works on its envs [bounds[k], bounds[k + 1]) on its own stream once every chunk's last
+    # step is done, and the results are concatenated in env order (complete: the caller's stream is ordered after the
+    # chunks).  An env slice of the arguments is strided, so every chunk gets its own contiguous copy, made on its stream.
     def lookahead(self, actions, bodies=False, objective=None, trace=False):
-        """VecMagicalEnv.lookahead for the whole pool: actions [H, num_envs] ([num_envs]: H = 1); chunk k runs its
-        columns [bounds[k], bounds[k + 1]) on its own stream once every chunk's last step is done, and the results
-        are concatenated in env order (complete: the caller's stream is ordered after the chunks).  objective and
-        trace as VecMagicalEnv.lookahead's, per chunk."""
-        kw = {} if objective is None and not trace else {"objective": objective, "trace": trace}
-        a = torch.as_tensor(actions)
-        if a.dim() == 1:
-            a = a[None]
-        if a.dim() != 2 or a.shape[1] != self.num_envs:
-            raise ValueError(f"lookahead: actions must be [H, {self.num_envs}], got {tuple(a.shape)}")
-        a = a.to(self.device, torch.uint8)
-        self.wait()
-        self._fork()
-        b, parts = self.bounds, []
-        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
-            with torch.cuda.stream(st):   # a column slice is strided: the chunk gets its own contiguous [H, m] copy
-                parts.append(sim.lookahead(a[:, b[k]:b[k + 1]].contiguous(), bodies=bodies, **kw))
-        self.wait()
-        out = collections.OrderedDict()
-        for key in parts[0]:   # envs are the first axis of every result but the [H, m] traces
-            out[key] = torch.cat([p[key] for p in parts], dim=-1 if key.endswith("_trace") else 0)
-            for p in parts:   # allocated on the chunks' streams, read here on the caller's
-                p[key].record_stream(self._caller())
-        return out
+        """VecMagicalEnv.lookahead for the whole pool: actions [H, num_envs] ([num_envs]: H = 1); objective and trace
+        as VecMagicalEnv.lookahead's, per chunk."""
+        a = seq_actions(actions, self.num_envs, "lookahead", "H", self.device)
+        return join(self._per_chunk(lambda k, sim, lo, hi: sim.lookahead(
+            a[:, lo:hi].contiguous(), bodies=bodies, objective=objective, trace=trace)), self._caller())
 
     def plan(self, actions, details=False, objective=None):
-        """VecMagicalEnv.plan for the whole pool: actions [H, K, num_envs] ([K, num_envs]: H = 1); chunk k plans its
-        envs [bounds[k], bounds[k + 1]) on its own stream once every chunk's last step is done, and the results are
-        concatenated in env order (complete: the caller's stream is ordered after the chunks).  objective as
+        """VecMagicalEnv.plan for the whole pool: actions [H, K, num_envs] ([K, num_envs]: H = 1); objective as
         VecMagicalEnv.plan's."""
-        from .envs import plan_actions
-        kw = {} if objective is None else {"objective": objective}
         a = plan_actions(actions, self.num_envs).to(self.device)
-        self.wait()
-        self._fork()
-        b, parts = self.bounds, []
-        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
-            with torch.cuda.stream(st):   # an env slice is strided: the chunk gets its own contiguous [H, K, m] copy
-                parts.append(sim.plan(a[:, :, b[k]:b[k + 1]].contiguous(), details=details, **kw))
-        self.wait()
-        out = collections.OrderedDict()
-        for key in parts[0]:
-            out[key] = torch.cat([p[key] for p in parts], dim=-1)   # envs are the last axis of every result
-            for p in parts:   # allocated on the chunks' streams, read here on the caller's
-                p[key].record_stream(self._caller())
-        return out
+        return join(self._per_chunk(lambda k, sim, lo, hi: sim.plan(
+            a[:, :, lo:hi].contiguous(), details=details, objective=objective)), self._caller())
 
     def plan_beam(self, actions, seg, survivors, details=False, objective=None):
-        """VecMagicalEnv.plan_beam for the whole pool, per chunk as plan(): chunk k searches for its envs [bounds[k],
-        bounds[k + 1]) on its own stream, and the results are concatenated in env order."""
-        from .envs import plan_actions
-        kw = {} if objective is None else {"objective": objective}
+        """VecMagicalEnv.plan_beam for the whole pool, per chunk as plan()."""
         a = plan_actions(actions, self.num_envs).to(self.device)
-        self.wait()
-        self._fork()
-        b, parts = self.bounds, []
-        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
-            with torch.cuda.stream(st):   # an env slice is strided: the chunk gets its own contiguous [H, K, m] copy
-                parts.append(sim.plan_beam(a[:, :, b[k]:b[k + 1]].contiguous(), seg, survivors, details=details, **kw))
-        self.wait()
-        out = collections.OrderedDict()
-        for key in parts[0]:
-            out[key] = torch.cat([p[key] for p in parts], dim=-1)   # envs are the last axis of every result
-            for p in parts:   # allocated on the chunks' streams, read here on the caller's
-                p[key].record_stream(self._caller())
-        return out
+        return join(self._per_chunk(lambda k, sim, lo, hi: sim.plan_beam(
+            a[:, :, lo:hi].contiguous(), seg, survivors, details=details, objective=objective)), self._caller())
 
     def sample_plans(self, H, K, repeat=1, key=42, step=0, out=None):
         """u8[H, K, num_envs] random-shooting candidates (VecMagicalEnv.sample_plans per chunk).  Chunk k draws with
@@ -367,58 +336,30 @@ class PipelinedVecEnv:
 
     def plan_cem(self, H, K, iters, elites, alpha=1, repeat=1, key=42, step=0, weights=None, details=False,
                  objective=None):
-        """VecMagicalEnv.plan_cem for the whole pool: chunk k plans its envs [bounds[k], bounds[k + 1]) on its own
-        stream with key + k (envs numbered from 0, as sample_plans), and the results are concatenated in env order.
-        weights: None, or a uint16 [J, 18, num_envs] tensor on the pool's device, the warm start, updated in place
-        (each chunk works on its own contiguous copy of its columns, which is copied back).  objective as
-        VecMagicalEnv.plan_cem's."""
-        kw = {} if objective is None else {"objective": objective}
+        """VecMagicalEnv.plan_cem for the whole pool, per chunk as plan(): chunk k draws with key + k (envs numbered
+        from 0, as sample_plans).  weights: None, or a uint16 [J, 18, num_envs] tensor on the pool's device, the warm
+        start, updated in place (each chunk works on its own contiguous copy of its columns, which is copied back).
+        objective as VecMagicalEnv.plan_cem's."""
         J = -(-int(H) // max(int(repeat), 1))
         if weights is not None and (not torch.is_tensor(weights) or tuple(weights.shape) != (J, 18, self.num_envs)
                                     or weights.dtype != torch.uint16 or weights.device != self.device):
             raise ValueError(f"plan_cem: weights must be a uint16 [{J}, 18, {self.num_envs}] tensor on {self.device}")
-        self.wait()
-        self._fork()
-        b, parts = self.bounds, []
-        for k, (sim, st) in enumerate(zip(self.sims, self.streams)):
-            with torch.cuda.stream(st):
-                w = (None if weights is None
-                     else weights.view(torch.int16)[:, :, b[k]:b[k + 1]].contiguous().view(torch.uint16))
-                parts.append(sim.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key + k, step=step,
-                                          weights=w, details=details, **kw))
-        self.wait()
-        out = collections.OrderedDict()
-        for name in parts[0]:
-            ts = [p[name] for p in parts]
-            if ts[0].dtype == torch.uint16:   # (moved as int16: the same bytes, a type every torch op takes)
-                out[name] = torch.cat([t.view(torch.int16) for t in ts], dim=-1).view(torch.uint16)
-            else:
-                out[name] = torch.cat(ts, dim=-1)   # envs are the last axis of every result
-            for p in parts:   # allocated on the chunks' streams, read here on the caller's
-                p[name].record_stream(self._caller())
+
+        def run(k, sim, lo, hi):   # (uint16 is sliced and copied as int16: the same bytes, a type every torch op takes)
+            w = None if weights is None else weights.view(torch.int16)[:, :, lo:hi].contiguous().view(torch.uint16)
+            return sim.plan_cem(H, K, iters, elites, alpha=alpha, repeat=repeat, key=key + k, step=step, weights=w,
+                                details=details, objective=objective)
+        out = join(self._per_chunk(run), self._caller())
         if weights is not None:
             weights.view(torch.int16).copy_(out["weights"].view(torch.int16))
             out["weights"] = weights
         return out
 
     def _obs(self):
-        from .envs import window_stack
-        allo, ego, past = self.buffers.get("allo"), self.buffers.get("ego"), self.buffers.get("past_obs")
-        if self.window_k:   # every chunk has stepped as often: one window start for the whole pool
-            s0, K = self.sims[0].window_start(), self.window_k
-            if self.spec.preproc == "LoResStack":
-                allo, ego = window_stack(self.wring[0], s0, K), window_stack(self.wring[1], s0, K)
-            else:
-                past = window_stack(self.wring[0] if self.wring[0] is not None else self.wring[1], s0, K)
-        out = collections.OrderedDict([("allo", allo), ("ego", ego)])
-        if self.sims[0]._chw:
-            out = collections.OrderedDict((k, v.permute(0, 3, 1, 2)) for k, v in out.items())
-        if self.target_f is not None:
-            t = self.target_f
-            out["target_type"], out["target_colour"], out["target_position"] = t[:, 0:1], t[:, 1:2], t[:, 2:4]
-        if past is not None:
-            out["past_obs"] = past.permute(0, 3, 1, 2) if self.sims[0]._chw else past
-        return out
+        # (every chunk has stepped as often: one window start for the whole pool)
+        return assemble_obs(self.buffers.get("allo"), self.buffers.get("ego"), self.buffers.get("past_obs"),
+                            self.wring if self.window_k else None, self.sims[0].window_start() if self.window_k else 0,
+                            self.sims[0]._chw, self.target_f)
 
     def random_actions(self, step, key=42, out=None):
         """Device Philox actions for a random policy (chunk k draws with key + k)."""
@@ -453,9 +394,7 @@ class PipelinedVecEnv:
         """VecMagicalEnv.rng_state of the whole pool: (key uint32 [num_envs, 624], pos int32 [num_envs])"""
         self.wait()
         parts = [sim.rng_state() for sim in self.sims]
-        # (torch.cat has no uint32 kernel: the keys are joined as int32 bits, as plan_cem's uint16 weights are)
-        key = torch.cat([k.view(torch.int32) for k, _ in parts]).view(torch.uint32)
-        return key, torch.cat([p for _, p in parts])
+        return cat_bits([k for k, _ in parts]), torch.cat([p for _, p in parts])
 
     def enable_timing(self, steps):
         """Per-chunk HIP-event timing of the kernels (mg_enable_timing on every chunk's simulator)."""

@@ -1171,3 +1171,56 @@ def test_pipelined_pool_matches_batch(name, n, chunks, L):
     assert int((pool.errors() != 0).sum()) == 0
     pool.close()
     ref.close()
+
+
+@pytest.mark.gpu
+def test_pipelined_pool_target_after_every_entry_point():
+    """PickAndPlace's target columns (and every other output) of a two-chunk pool against the flat batch after each
+    call that rewrites the target: reset(), step_seq() with an auto-reset inside the call, restore(), reset_scenes()
+    with a mask over both chunks, and step()."""
+    from magical_amd import pipeline
+    name, n, L = "PickAndPlace-Demo-LoResCHW4A-v0", 8, 6
+    seeds = [1000 + i for i in range(n)]
+    ref = mg_envs.VecMagicalEnv(name, n, seeds=seeds, max_episode_steps=L)
+    pool = pipeline.PipelinedVecEnv(name, n, chunks=2, seeds=seeds, max_episode_steps=L)
+    assert pool.bounds == [0, 4, 8]
+    acts = torch.from_numpy(np.random.RandomState(42).randint(0, 18, (12, n)).astype(np.uint8))
+
+    def same(o_ref, o_pool, at):
+        pool.wait()
+        assert list(o_ref) == list(o_pool) and all(k in o_pool for k in mg_envs.TARGET_KEYS), at
+        for k in o_ref:
+            assert torch.equal(o_ref[k], o_pool[k]), (at, k)
+        for k, v in (("reward", ref.reward), ("done", ref.done), ("eval_score", ref.eval_score)):
+            assert torch.equal(v, pool.buffers[k]), (at, k)
+        if ref.seq_steps is not None:
+            assert torch.equal(ref.seq_steps, pool.seq_steps), (at, "steps")
+
+    same(ref.reset(), pool.reset(), "reset")
+    ended = torch.zeros(n, dtype=torch.bool, device="cuda:0")
+    for i in range(2):   # 4 + 2 env-steps: every env ends its episode in the second call and is auto-reset there
+        a = acts[4 * i:4 * i + 4]
+        (o_ref, _, d_ref, i_ref), (o_pool, _, _, i_pool) = ref.step_seq(a), pool.step_seq(a)
+        same(o_ref, o_pool, ("step_seq", i))
+        assert i_pool["steps"] is pool.seq_steps and i_ref["steps"] is ref.seq_steps
+        ended |= d_ref
+    assert bool(ended.all())
+    snap, at_snap = pool.snapshot(), {k: v.clone() for k, v in o_pool.items()}
+    for t in range(8, 11):
+        (o_ref, *_), (o_pool, *_) = ref.step(acts[t]), pool.step(acts[t])
+        same(o_ref, o_pool, ("step", t))
+    o_ref, o_pool = ref.restore(snap), pool.restore(snap)
+    same(o_ref, o_pool, "restore")
+    for k in at_snap:
+        assert torch.equal(at_snap[k], o_pool[k]), ("restore shows the recorded observation", k)
+    scenes = pool.get_scenes()
+    assert scenes.tobytes() == ref.get_scenes().tobytes()
+    mask = torch.tensor([1, 0, 1, 0, 0, 1, 1, 0], dtype=torch.bool)
+    (o_ref, s_ref), (o_pool, s_pool) = ref.reset_scenes(scenes, mask=mask), pool.reset_scenes(scenes, mask=mask)
+    same(o_ref, o_pool, "reset_scenes")
+    assert torch.equal(s_ref, s_pool) and s_pool.tolist() == [0, -1, 0, -1, -1, 0, 0, -1]
+    (o_ref, *_), (o_pool, *_) = ref.step(acts[11]), pool.step(acts[11])
+    same(o_ref, o_pool, "step after reset_scenes")
+    assert int((pool.errors() != 0).sum()) == 0
+    pool.close()
+    ref.close()
