@@ -3,23 +3,18 @@
 // step kernel's table (mg_stepforms.h), in translation units of their own (mg_look_quad.hip: 5 / 6, mg_look_v4.hip:
 // 4, mg_look_hbm.hip: 0); mg_lookahead.hip dispatches.
 //
-// The kernel is built from step_kernel's pieces (mg_stepk.h) with the env-step loop inside: StepForm (what the pair
-// fixes at compile time), xcd_block, carve_view, xfer_state_quad and xfer_state (the LDS view and its transfers), the
-// env_substeps_* calls in step_kernel's order, and launch_env_kernel; the lane map, scene check and quad entry are
-// written out here as there ("One workgroup skeleton", says why) -- so an env's state
-// after h iterations has the bits that h calls of mg_step give it (everything is compiled with -ffp-contract=off,
-// and what the view does not carry from one env-step to the next -- cached shape BBs, the constraints' pre-step
-// products, the robot's targets and motor rates -- is recomputed before use in every env-step, here as there).
-// Its own: the view is loaded once and written back once, S is the sim's scratch pool (never its own state),
-// and there is no episode counter, reward, done flag or reset -- only the outputs of LookOut.
+// The kernel is step_kernel's lane map (mg_lanes.h), the env-step loop (mg_rollout.h: the scene check, the loop and its
+// barrier protocol, one text shared with step_seq_kernel, and why an env's state after h iterations has the bits that h
+// calls of mg_step give it) and then its own tail.  S is the sim's scratch pool (never its own state), and there is no
+// episode counter, reward, done flag or reset -- only the outputs of LookOut.
 //
-// TRACE (mg_lookahead_obj, mg_plan_obj, mg_plan_cem_obj; a second instantiation of every pair): the env's view goes
-// back to its scratch column after EVERY env-step, as mg_step's does, and the env's scoring lane evaluates the task's
-// score s_k and mg_step's reward r_k there with score_env / debug_reward as they are -- the bits of mg_step's scoring
-// by construction -- and accumulates the objective (LookObj, mg_launch.h; the definitions: include/magical_sim.h and
-// DESIGN.md).  mg_plan_beam continues an objective over several launches on one pool through LookObj.carry: the
-// accumulators are stored per rollout on exit and, when the carry says so, loaded on entry in place of obj_begin.
-// Everything TRACE adds is under `if constexpr (TRACE)`.
+// TRACE (mg_lookahead_obj, mg_plan_obj, mg_plan_cem_obj; a second instantiation of every pair; the loop's EVERY): the
+// env's view goes back to its scratch column after EVERY env-step, as mg_step's does, and the env's scoring lane
+// evaluates the task's score s_k and mg_step's reward r_k there with score_env / debug_reward as they are -- the bits of
+// mg_step's scoring by construction -- and accumulates the objective (LookObj, mg_launch.h; the definitions:
+// include/magical_sim.h and DESIGN.md).  mg_plan_beam continues an objective over several launches on one pool through
+// LookObj.carry: the accumulators are stored per rollout on exit and, when the carry says so, loaded on entry in place
+// of obj_begin.
 #pragma once
 #include "mg_stepk.h"
 
@@ -30,19 +25,7 @@ MG_DEV void look_emit(const MGState &S, const mg_library *L, int e, int task, in
     if constexpr (SCORE) o.score[e] = score_env(S, L, e, task);
     if (o.steps) o.steps[e] = n;
     if (o.errors) o.errors[e] = S.overflow[e];
-    if (o.bodies) {   // as bodies_kernel (mg_get_bodies)
-        const int nb = S.nbodies[e];
-        for (int b = 0; b < MG_MAX_BODIES; b++) {
-            double *q = o.bodies + ((size_t)e * MG_MAX_BODIES + b) * 6;
-            const bool live = b < nb;
-            q[0] = live ? AT(S.bpx, b) : 0.0; q[1] = live ? AT(S.bpy, b) : 0.0; q[2] = live ? AT(S.ba, b) : 0.0;
-            q[3] = live ? AT(S.bvx, b) : 0.0; q[4] = live ? AT(S.bvy, b) : 0.0; q[5] = live ? AT(S.bw, b) : 0.0;
-        }
-    }
-    if (o.counts) {
-        o.counts[4 * e + 0] = S.nbodies[e]; o.counts[4 * e + 1] = S.nshapes[e];
-        o.counts[4 * e + 2] = S.ncons[e]; o.counts[4 * e + 3] = S.nactive[e];
-    }
+    env_bodies_record(S, e, o.bodies, o.counts);
 }
 
 // ---- TRACE: the objective's accumulators, in registers of the env's scoring lane --------------------------------
@@ -116,18 +99,7 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
                                                        const uint8_t *__restrict__ actions, int H, LookOut out, LookObj obj) {
     extern __shared__ __align__(16) unsigned char smem[];
     using F = StepForm<VAR, BLK>;
-    constexpr StepCaps C = F::C;
-    const int lane = F::COOP ? (int)threadIdx.x : F::QUAD ? (int)threadIdx.x / F::QL : BLK == 1 ? 0 : (int)threadIdx.x;
-    const int sub = F::QUAD ? (int)threadIdx.x % F::QL : 0;
-    int e = xcd_block(blockIdx.x, gridDim.x) * BLK + (F::COOP ? 0 : lane);
-    // QUAD: lanes without an env of their own (past n_envs, or a scene the form cannot hold) take part in the
-    // workgroup barriers as shadows of a valid env and never write HBM: step_kernel's convention
-    bool shadow = false;
-    if (e >= S.n_envs) {
-        if (!F::QUAD) return;
-        shadow = true;
-        e = S.n_envs - 1;
-    }
+#include "mg_lanes.h"
     const uint8_t *act = actions + e;   // step h: act[h * n_envs], h < H and e < n_envs
     const size_t astride = (size_t)S.n_envs;
     int n = H;
@@ -148,103 +120,21 @@ __global__ void __launch_bounds__(64) lookahead_kernel(MGState S, const mg_libra
             else obj_begin(acc, S, L, e, task);
         }
     }
-    MGProf P;
-    MG_PP_INIT(P);
-    if constexpr (F::LDS) {
-        bool fits = true;
-        if (S.nbodies[e] > C.nb || S.nshapes[e] > C.ns || S.ncons[e] > C.nc) {
-            if (!shadow && sub == 0) S.overflow[e] |= 16; // scene larger than the variant's LDS caps (never expected)
-            fits = false;
-        }
-        bool ok = F::NCS == 0 || (S.ncons[e] == C.nc && S.robot_body0[e] == 0 && S.robot_cons0[e] == 0);
-        for (int c = 0; c < F::NCS; c++) {
-            const ConsDesc d = static_cons(c);
-            ok = ok && AT(S.ctype, c) == d.type && AT(S.ca, c) == d.a && AT(S.cb, c) == d.b;
-        }
-        for (int k = 0; k < S.nshapes[e] && k < C.ns && F::NCS > 0; k++) ok = ok && shape_body_slot(AT(S.sbody, k)); // arb_body
-        if (!ok && fits && !shadow && sub == 0) S.overflow[e] |= 32; // the compiled constraint list does not describe this scene
-        if (!F::QUAD && !(fits && ok)) {   // COOP, uniform over the workgroup: nothing is simulated
-            if (lane == 0) {
-                if constexpr (TRACE) obj_emit(acc, S, L, e, task, 0, H, false, out, obj);
-                else look_emit(S, L, e, task, 0, out);
-            }
-            return;
-        }
-        MGState V = S;
-        carve_view(V, smem, C, BLK);
-        if constexpr (F::QUAD) {
-            const bool own = !shadow && fits && ok;
-            if (!own) n = 0;
-            xfer_state_quad<C.nb, C.ns, C.nc, C.na, F::QL>(S, V, lane, e, sub);
-            if (!fits && sub == 0) { // an empty scene in the env's column: nothing indexes past the caps
-                V.nbodies[lane] = 0; V.nshapes[lane] = 0; V.ncons[lane] = 0; V.nactive[lane] = 0;
-            }
-            // every lane meets the workgroup barriers until the workgroup's longest env is done (all 64 lanes are
-            // here: nothing has returned)
-            int hw = n;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const int o = __shfl_xor(hw, off, 64);
-                hw = o > hw ? o : hw;
-            }
-            for (int h = 0; h < hw; h++) {
-                env_substeps_quad<F::NCS, F::QL>(V, L, lane, sub, act[h * astride], P);   // ends with a workgroup barrier
-                if constexpr (TRACE) {
-                    // Every env-step of the env's own n: its column goes back to scratch from its own lanes, between
-                    // that closing barrier and the barrier below (no lane writes the view there: the next env-step
-                    // writes it only behind its opening barrier).  The fence and barrier publish the rows to the env's
-                    // sub-lane 0, which then scores from scratch -- HBM reads only, so the other lanes may run on into
-                    // the next env-step's opening barrier and wait there.  hw is uniform over the workgroup (the
-                    // butterfly above) and nothing returns or breaks inside the loop, so all 64 lanes -- shadows and
-                    // envs past their n included -- reach this barrier exactly hw times, as they do those of
-                    // env_substeps_quad.  An env past its n (and a shadow, n = 0) goes on in LDS and touches neither
-                    // its scratch column nor its outputs again: both are guarded by own && h < n, and h < n <= H,
-                    // e < n_envs bound the trace index (obj_step).
-                    if (own && h < n) xfer_state(S, V, C, lane, e, false, false, sub, F::QL);
-                    __threadfence_block();
-                    __syncthreads();
-                    if (own && sub == 0 && h < n) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);
-                } else {
-                    // the env's last step: its column goes back to scratch from its own lanes, between that barrier and
-                    // the next env-step's opening one (no lane writes the view there); afterwards the env goes on in LDS
-                    // as a shadow does and never writes HBM again
-                    if (own && h + 1 == n) xfer_state(S, V, C, lane, e, false, false, sub, F::QL);
-                }
-            }
-            // the env's lane 0 reads scratch rows its sibling lanes wrote back: ordered by the memory model (as
-            // step_kernel)
-            __threadfence_block();
-            __syncthreads();
-            if (shadow || sub != 0) return;
-        } else {   // COOP
-            xfer_state(S, V, C, 0, e, true, true, lane, 64);
-            __syncthreads();
-            for (int h = 0; h < n; h++) {
-                env_substeps_coop(V, L, lane, act[h * astride], P);   // ends with a workgroup barrier
-                if constexpr (TRACE) {
-                    // all 64 lanes write the view back (n is uniform: one env per workgroup), fence and barrier, then
-                    // lane 0 scores from scratch.  It reads HBM only and the view is next written behind the next
-                    // env-step's first barrier, which waits for lane 0: no barrier is needed after the scoring
-                    xfer_state(S, V, C, 0, e, false, true, lane, 64);
-                    __threadfence_block();
-                    __syncthreads();
-                    if (lane == 0) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);
-                }
-            }
-            // (TRACE: the scratch holds x_n already -- the last step's write-back, or the untouched copy when n = 0)
-            if constexpr (!TRACE) xfer_state(S, V, C, 0, e, false, true, lane, 64);
-            __threadfence_block();
-            __syncthreads();
-            if (lane != 0) return;
-        }
-    } else {
-        for (int h = 0; h < n; h++) {
-            env_substeps(S, L, e, act[h * astride], P);
-            if constexpr (TRACE) obj_step(acc, S, L, e, task, h, done_n && h + 1 == n, obj);   // form 0 steps S itself
-        }
-    }
-    if constexpr (TRACE) obj_emit(acc, S, L, e, task, n, H, done_n, out, obj);
-    else look_emit(S, L, e, task, n, out);
+    // a refused env has its error flag in the scratch's `overflow` and emits its outputs with n = 0
+#define LOOK_EMIT(steps, ends) \
+    do { \
+        if constexpr (TRACE) obj_emit(acc, S, L, e, task, (steps), H, (ends), out, obj); \
+        else look_emit(S, L, e, task, (steps), out); \
+    } while (0)
+#define MG_ROLLOUT_EVERY TRACE
+#define MG_ROLLOUT_IF_BOTH(a, b) if ((a) && (b))
+#define MG_ROLLOUT_REFUSE() do { } while (0)
+#define MG_ROLLOUT_REFUSED_COOP() do { if (lane == 0) LOOK_EMIT(0, false); } while (0)
+#define MG_ROLLOUT_REFUSED_TAIL true
+#define MG_ROLLOUT_AFTER_STEP(h) obj_step(acc, S, L, e, task, (h), done_n && (h) + 1 == n, obj)
+#include "mg_rollout.h"
+    LOOK_EMIT(n, done_n);
+#undef LOOK_EMIT
 }
 
 template <int VAR, int BLK, bool TRACE>

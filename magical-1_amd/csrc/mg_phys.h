@@ -18,6 +18,24 @@
 #define ACON(k, f, a) S.acon[(((uint32_t)(k) * AC_NUM + (uint32_t)(f)) * (uint32_t)S.arb_cap + (uint32_t)(a)) * (uint32_t)S.N + (uint32_t)e]
 #define AHASH(k, a) S.ahash[((uint32_t)(k) * (uint32_t)S.arb_cap + (uint32_t)(a)) * (uint32_t)S.N + (uint32_t)e]
 
+// env e's record of mg_get_bodies and of mg_lookahead's `bodies` / `counts` (either may be null; one lane per env):
+// bodies f64[n_envs][MG_MAX_BODIES][6] = x, y, angle, vx, vy, w, zeros past the env's bodies; counts i32[n_envs][4]
+MG_DEV void env_bodies_record(const MGState &S, int e, double *bodies, int32_t *counts) {
+    if (bodies) {
+        const int nb = S.nbodies[e];
+        for (int b = 0; b < MG_MAX_BODIES; b++) {
+            double *q = bodies + ((size_t)e * MG_MAX_BODIES + b) * 6;
+            const bool live = b < nb;
+            q[0] = live ? AT(S.bpx, b) : 0.0; q[1] = live ? AT(S.bpy, b) : 0.0; q[2] = live ? AT(S.ba, b) : 0.0;
+            q[3] = live ? AT(S.bvx, b) : 0.0; q[4] = live ? AT(S.bvy, b) : 0.0; q[5] = live ? AT(S.bw, b) : 0.0;
+        }
+    }
+    if (counts) {
+        counts[4 * e + 0] = S.nbodies[e]; counts[4 * e + 1] = S.nshapes[e];
+        counts[4 * e + 2] = S.ncons[e]; counts[4 * e + 3] = S.nactive[e];
+    }
+}
+
 struct V2 { double x, y; };
 MG_DEV V2 v2(double x, double y) { return {x, y}; }
 MG_DEV V2 vadd(V2 a, V2 b) { return {a.x + b.x, a.y + b.y}; }

@@ -4,8 +4,6 @@
 // (their A/B results are in DESIGN.md).  mg_step_seq's kernels (mg_seq.h, mg_seq_*.hip) are dispatched here likewise.
 #include "mg_launch.h"
 
-hipError_t mg_prof_read_step_quad(unsigned long long *out64);   // mg_step_quad.hip
-
 hipError_t mg_launch_step(const MGState &S, const mg_library *L, TaskCfg cfg, int form, int blk, int max_steps,
                           int auto_reset, const uint8_t *actions, float *reward, uint8_t *done, double *eval_score,
                           uint8_t *reset_mask, hipStream_t st) {

@@ -25,19 +25,7 @@ int set_err(int code, const std::string &msg) {
 __global__ void __launch_bounds__(64) bodies_kernel(MGState S, double *out, int32_t *counts) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= S.n_envs) return;
-    for (int b = 0; b < MG_MAX_BODIES; b++) {
-        double *o = out + ((size_t)e * MG_MAX_BODIES + b) * 6;
-        if (b < S.nbodies[e]) {
-            o[0] = AT(S.bpx, b); o[1] = AT(S.bpy, b); o[2] = AT(S.ba, b);
-            o[3] = AT(S.bvx, b); o[4] = AT(S.bvy, b); o[5] = AT(S.bw, b);
-        } else {
-            for (int k = 0; k < 6; k++) o[k] = 0.0;
-        }
-    }
-    if (counts) {
-        counts[4 * e + 0] = S.nbodies[e]; counts[4 * e + 1] = S.nshapes[e];
-        counts[4 * e + 2] = S.ncons[e]; counts[4 * e + 3] = S.nactive[e];
-    }
+    env_bodies_record(S, e, out, counts);
 }
 
 // the solved arbiters of every env in active order (oracle/env.c oenv_get_arbiters has the same layout)

@@ -1,7 +1,8 @@
-// mg_stepk.h -- the step kernel template (action decode, 10 x [Robot.update + cpSpaceStep], episode
-// counter, score) and its launcher.  Each form is instantiated in its own translation unit
-// (mg_step_quad.hip: 5 / 6, mg_step_v4.hip: 4, mg_step_hbm.hip: 0) so they compile in parallel;
-// mg_physics.hip dispatches.  The forms, their slot caps and the LDS view's arrays: mg_stepforms.h.
+// mg_stepk.h -- the step kernel template (action decode, 10 x [Robot.update + cpSpaceStep], episode counter, score) and
+// its launcher, with the pieces step_seq_kernel (mg_seq.h) and lookahead_kernel (mg_lookahead.h) are built from as well
+// (their env-step loop: mg_rollout.h).  Each form is instantiated in its own translation unit (mg_step_quad.hip: 5 / 6,
+// mg_step_v4.hip: 4, mg_step_hbm.hip: 0) so they compile in parallel; mg_physics.hip dispatches.  The forms, their slot
+// caps and the LDS view's arrays: mg_stepforms.h.
 #pragma once
 #include <cstdio>
 #include "mg_launch.h"
@@ -201,9 +202,11 @@ __device__ __forceinline__ void env_substeps_coop(const MGState &V, const mg_lib
     }
 }
 
-// What a (form, envs per workgroup) pair fixes at compile time, for step_kernel and lookahead_kernel (mg_lookahead.h)
-// alike.  (The lane map, scene check and quad entry that follow it in both kernels are still written out in each:
-// moved into shared functions, the quad kernels' register figures changed -- DESIGN.md, "One workgroup skeleton".)
+// What a (form, envs per workgroup) pair fixes at compile time, for step_kernel and the two looping kernels (mg_rollout.h)
+// alike.  step_kernel shares the lane map with them (mg_lanes.h) and keeps its scene check, quad entry and episode tail
+// written out, although mg_rollout.h and step_seq_kernel's tail repeat them: it is the benchmarked kernel, its cooperative
+// form holds two wavefronts per SIMD at exactly 256 VGPRs, and moved into shared functions those pieces changed the quad
+// kernels' register figures ("One workgroup skeleton").
 template <int VAR, int BLK>
 struct StepForm {
     static_assert(mg_step_blk_ok(VAR, BLK), "not a pair of MG_STEP_FORMS (mg_stepforms.h)");
@@ -222,17 +225,7 @@ __global__ void __launch_bounds__(64) step_kernel(MGState S, const mg_library *_
     extern __shared__ __align__(16) unsigned char smem[];
     using F = StepForm<VAR, BLK>;
     constexpr StepCaps C = F::C;
-    const int lane = F::COOP ? (int)threadIdx.x : F::QUAD ? (int)threadIdx.x / F::QL : BLK == 1 ? 0 : (int)threadIdx.x;
-    const int sub = F::QUAD ? (int)threadIdx.x % F::QL : 0;
-    int e = xcd_block(blockIdx.x, gridDim.x) * BLK + (F::COOP ? 0 : lane);
-    // QUAD: lanes without an env of their own (past n_envs, or a scene the form cannot hold) still take
-    // part in the workgroup barriers as shadows of a valid env; they never write HBM
-    bool shadow = false;
-    if (e >= S.n_envs) {
-        if (!F::QUAD) return;
-        shadow = true;
-        e = S.n_envs - 1;
-    }
+#include "mg_lanes.h"
     const int a = actions[e];
     MGProf P;
     MG_PP_INIT(P);
