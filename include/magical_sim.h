@@ -508,6 +508,48 @@ typedef struct {
  * ranges above, or an objective that mg_plan_obj refuses. */
 int mg_plan_beam(mg_sim *sim, const uint8_t *actions_dev, uint8_t *plans_dev, int32_t H, int32_t K, int32_t seg,
                  int32_t survivors, const mg_objective *objective, const mg_plan_beam_out *out, void *stream);
+
+/* ---- imagined observations: the LoRes frames of a lookahead rollout ----
+ * What the agent would SEE if these actions were played: mg_lookahead's rollout, rendered every `every` env-steps.
+ * F = ceil(H / every) frames per env; segment f is the steps [f*every, min(H, (f+1)*every)).  All four buffers are
+ * device memory, 16-byte aligned, HWC as a frames_only binding's (mg_buffers). */
+typedef struct {
+    uint8_t *allo;        /* u8[F][N][96][96][3]: the current allo frame after segment f; NULL ok */
+    uint8_t *ego;         /* u8[F][N][96][96][3]; NULL ok */
+    uint8_t *stack_allo;  /* u8[F][N][96][96][12]; NULL ok; see the stack rules */
+    uint8_t *stack_ego;   /* u8[F][N][96][96][12]; NULL ok */
+} mg_imagine_out;
+/* actions_dev: device u8[H][N] as mg_lookahead's.  1 <= H <= 4096, 1 <= every <= H.  The per-env horizon is
+ * mg_lookahead's: n = min(H, remaining); an env whose episode ends inside the horizon stops at its terminal step.
+ *
+ * Frames.  Frame f of env e is the LoRes current frame -- the bytes a frames_only binding receives for that view, for
+ * every LoRes preprocessor -- of the state after m_f = min((f+1)*every, n) env-steps.  Frames of an env that has
+ * stopped repeat its terminal state's frame; there is no auto-reset, as in mg_lookahead.  Within an episode frame f is
+ * the current frame the f+1-th of F successive mg_step_seq(actions + f*every*N, every) calls would show.
+ *
+ * Lookahead outputs.  `out` may be NULL, and if given its score may be NULL too.  score, steps, bodies and counts
+ * receive bit for bit what mg_lookahead(sim, actions_dev, H, out) writes; errors the same OR-ed with any raster
+ * capacity flag (4 / 8) raised while the imagined frames were drawn.
+ *
+ * Stacks: what the preprocessor's frame stacking would hold after those calls.  With g_f = frame f and g_-1, g_-2,
+ * g_-3 the env's three most recent real frames (the sim's frame ring, newest = -1), stack[f] = (g_f-3, g_f-2, g_f-1,
+ * g_f), oldest first: channel k = channel k%3 of frame k/3.  Legal: LoResStack stack_allo and stack_ego; LoRes4E
+ * stack_ego; LoRes4A stack_allo; LoRes3EA stack_ego = allo_f | ego_f-2 | ego_f-1 | ego_f (its past_obs layout), which
+ * needs both allo and ego.  A stack needs the plain frame buffer(s) it is built from.  After an env's terminal step the
+ * repeated frame keeps entering the stack: those stacks correspond to no real step.  Stacks read the sim's own frame
+ * history, which a handle with window rings or frames_only outputs does not keep: -22 there (mg_snapshot's rule);
+ * plain frames work in every LoRes mode.
+ *
+ * The sim is observationally untouched, exactly as stated for mg_lookahead (frame rings, static layer, window rings
+ * and position, bound outputs and the next-layout shadow included).  The call runs on mg_lookahead's scratch pool
+ * (allocated by the first call of either, which alone synchronises) and allocates nothing else; every segment's
+ * rollout launch and render and the final stack pass are enqueued on `stream` with no host sync; every == H is one
+ * rollout launch.
+ * Returns -22 and launches nothing for a null sim / actions_dev / frames, all four frame buffers null, H or every out
+ * of range, a misaligned buffer, the unwrapped surface (preproc 0), a stack not legal for the preprocessor, or a stack
+ * without its plain frames. */
+int mg_imagine(mg_sim *sim, const uint8_t *actions_dev, int32_t H, int32_t every, const mg_lookahead_out *out,
+               const mg_imagine_out *frames, void *stream);
 void mg_destroy(mg_sim *sim);
 const char *mg_last_error(void);
 

@@ -98,6 +98,9 @@ hipError_t launch_look(const MGState &S, const mg_library *L, int task, int max_
 // obj null: the plain kernel; else the TRACE one
 hipError_t mg_launch_lookahead(const MGState &S, const mg_library *L, int task, int form, int blk, int max_steps,
                                const uint8_t *actions, int H, const LookOut &out, const LookObj *obj, hipStream_t st);
+// mode 0: LoRes outputs (window rings where ro has them), 1: full resolution, 3: mg_imagine's form -- S is a pool without
+// frame rings, ro.obs_allo / ro.obs_ego (either may be null: that view is not drawn) receive the plain current frames,
+// and only ro's preproc, small, first_level and force_retry are read besides
 hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderOut &ro, int mode, hipStream_t st);
 hipError_t mg_launch_compose3ea(const MGState &S, const uint8_t *obs_allo, const uint8_t *mask, uint8_t *obs_past,
                                 hipStream_t st);

@@ -2,15 +2,22 @@
 #include "mg_launch.h"
 #include "mg_render.h"
 
+// one capacity class in the launch's mode (3: mg_imagine's frame-less form, mg_render.h)
+#define RG_LAUNCH(CLS) \
+    do { \
+        if (mode == 0) hipLaunchKernelGGL((render_kernel<RenderSmem<CLS>, 0>), grid, blk, 0, st, S, L, r); \
+        else if (mode == 2) hipLaunchKernelGGL((render_kernel<RenderSmem<CLS>, 2>), grid, blk, 0, st, S, L, r); \
+        else if (mode == 3) hipLaunchKernelGGL((render_kernel<RenderSmem<CLS>, 3>), grid, blk, 0, st, S, L, r); \
+        else hipLaunchKernelGGL((render_kernel<RenderSmem<CLS>, 1>), grid, blk, 0, st, S, L, r); \
+    } while (0)
+
 hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderOut &ro, int mode, hipStream_t st) {
     const dim3 grid(S.n_envs, 2), blk(RG_THREADS);
     RenderOut r = ro;
     r.retry_in = r.retry_out = r.cls_level = 0;
     if (mode == 0 && (ro.wring[0] || ro.wring[1]) && !ro.frames_only) mode = 2;   // window rings: own kernels
     if (ro.small) {   // the small class holds every MoveToRegion / MoveToCorner scene
-        if (mode == 0) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_SMALL>, 0>), grid, blk, 0, st, S, L, r);
-        else if (mode == 2) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_SMALL>, 2>), grid, blk, 0, st, S, L, r);
-        else hipLaunchKernelGGL((render_kernel<RenderSmem<RG_SMALL>, 1>), grid, blk, 0, st, S, L, r);
+        RG_LAUNCH(RG_SMALL);
         return hipGetLastError();
     }
     // many-block tasks: a chain of classes, each with more LDS (fewer workgroups per CU) than the last.  A
@@ -24,30 +31,23 @@ hipError_t mg_launch_render(const MGState &S, const mg_library *L, const RenderO
     r.retry_in = 1; r.retry_out = 1;
     hipError_t e;
     if (r.first_level == 0) {
-        if (mode == 0) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM0>, 0>), grid, blk, 0, st, S, L, r);
-        else if (mode == 2) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM0>, 2>), grid, blk, 0, st, S, L, r);
-        else hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM0>, 1>), grid, blk, 0, st, S, L, r);
+        RG_LAUNCH(RG_MEDIUM0);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     r.cls_level = 1;
-    if (mode == 0) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM1>, 0>), grid, blk, 0, st, S, L, r);
-    else if (mode == 2) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM1>, 2>), grid, blk, 0, st, S, L, r);
-    else hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM1>, 1>), grid, blk, 0, st, S, L, r);
+    RG_LAUNCH(RG_MEDIUM1);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     r.cls_level = 2;
-    if (mode == 0) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM2>, 0>), grid, blk, 0, st, S, L, r);
-    else if (mode == 2) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM2>, 2>), grid, blk, 0, st, S, L, r);
-    else hipLaunchKernelGGL((render_kernel<RenderSmem<RG_MEDIUM2>, 1>), grid, blk, 0, st, S, L, r);
+    RG_LAUNCH(RG_MEDIUM2);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     r.retry_out = 0; r.cls_level = 3;
-    if (mode == 0) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_LARGE>, 0>), grid, blk, 0, st, S, L, r);
-    else if (mode == 2) hipLaunchKernelGGL((render_kernel<RenderSmem<RG_LARGE>, 2>), grid, blk, 0, st, S, L, r);
-    else hipLaunchKernelGGL((render_kernel<RenderSmem<RG_LARGE>, 1>), grid, blk, 0, st, S, L, r);
+    RG_LAUNCH(RG_LARGE);
     return hipGetLastError();
 }
+#undef RG_LAUNCH
 
 // LoRes3EA (benchmarks/__init__.py lores_ea_entry_point: FlattenFrameStack with allo depth 1, ego
 // depth 3): past_obs[y][x] = allo_t | ego_t-2 | ego_t-1 | ego_t (12 bytes per pixel). The two views are

@@ -486,7 +486,11 @@ MG_DEV int xf_slot(int ent, int x) { return x == MG_XF_MAIN ? ent : SM::RG_MAXE 
 
 // One (env, view) per workgroup.  MODE 0: LoRes outputs; 1: full-resolution frames; 2: LoRes outputs with the
 // stacked views as window rings (RenderOut::wring) -- its own instantiation, so the materialising kernels carry
-// none of its code (a shared build measured 4% slower render kernels, round 5).
+// none of its code (a shared build measured 4% slower render kernels, round 5).  MODE 3 (mg_imagine): the plain current
+// frame of each view -- the bytes of a frames-only binding -- from a pool WITHOUT frame rings (a rollout pool, mg_pool.h:
+// hist_*, hist_head, scache and scache_ok are null and never touched), so no stack, no ring write and no static layer
+// (every block is resolved); a view whose output pointer is null is not drawn.  Every use of IMG below is a constant of
+// the instantiation: modes 0-2 compile to what they did without it.
 #ifndef RG_SMALL_WPE
 #define RG_SMALL_WPE 7                  // waves per SIMD the small class is compiled for: 72 VGPRs, 9 workgroups/CU
                                         // (measured: 7 -> 2.5% faster than the default 6; 8 = 64 VGPRs slower)
@@ -503,10 +507,12 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     constexpr int RG_STKT = RG_BROWS * MG_LORES / 4, RG_RING0 = RG_STKT > 64 ? RG_STKT : 64;
     constexpr int RG_BANDLO = RG_BROWS * RG_LOROW, RG_BANDLO16 = SM::BANDLO16;
     constexpr int RG_CPF0 = RG_THREADS - RG_BANDLO16 < 128 ? RG_THREADS - RG_BANDLO16 : 128;
-    constexpr int mode = MODE == 2 ? 0 : MODE;
-    constexpr bool WIN = MODE == 2;
+    constexpr int mode = (MODE == 2 || MODE == 3) ? 0 : MODE;
+    constexpr bool WIN = MODE == 2, IMG = MODE == 3;
     const int e = blockIdx.x, view = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     if (e >= S.n_envs || (out.mask && !out.mask[e])) return;
+    if constexpr (IMG)
+        if (!(view == 0 ? out.obs_allo : out.obs_ego)) return;
     // class chain (many-block tasks): S.rg_retry[e][view] holds the chain level that holds this (env, view)
     // in the current episode -- scenes keep their entities for an episode, so a pair that overflowed a class
     // skips it on later frames instead of rebuilding its setup there first.  An episode's first frame starts
@@ -521,7 +527,7 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     // an episode's first allo frame invalidates the static layer of the previous episode before anything can
     // fail: a frame that a class hands over (or gives up on) must not leave the old layer marked valid
     // (ADVICE r3); a successful first frame of the layer's class sets it again at the end
-    if (mode == 0 && view == 0 && tid == 0 && S.scache_ok && S.episode_steps[e] == 0) S.scache_ok[e] = 0;
+    if (!IMG && mode == 0 && view == 0 && tid == 0 && S.scache_ok && S.episode_steps[e] == 0) S.scache_ok[e] = 0;
     MG_PROF_BEGIN(tid == 0);
     // capacity overflow: a class with a successor hands the (env, view) to it, else an env error
 #define RG_FAIL() do { \
@@ -849,12 +855,12 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     uint8_t *ring = view == 0 ? S.hist_allo : S.hist_ego;
     const size_t FR = (size_t)MG_LORES * MG_LORES * 3;
     const bool fresh = S.episode_steps[e] == 0;
-    const int head = S.hist_head[view * S.N + e];
+    const int head = IMG ? 0 : S.hist_head[view * S.N + e];
     const int nh = fresh ? 0 : ((head + 1) & 3);
     const int pp = out.preproc;
     // frames-only outputs (compact multi-GPU gather): the current frame of each view, no stacks, no ring
     // (the receivers rebuild the stacks: mg_restack)
-    const bool fo = out.frames_only != 0;
+    const bool fo = IMG || out.frames_only != 0;
     const bool stacked0 = !fo && (pp == MG_PREPROC_LORESSTACK || (pp == MG_PREPROC_LORES4E && view == 1) ||
                                   (pp == MG_PREPROC_LORES4A && view == 0));
     // window ring (mg_bind_window): the stack of this view is a strided view of a ring the current frame is
@@ -877,7 +883,7 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     // The many-block tasks' classes are compiled without it: their scenes' blocks reach most bands, and
     // the layer's code measured slower there (ClusterColour 2.72 -> 3.00 ms, MatchRegions 3.37 -> 3.41 ms).
     constexpr bool kLayer = RG_SCACHE && SM::RG_MAXG <= 32;
-    const bool cview = kLayer && mode == 0 && view == 0 && out.scache_mode != 1 && !keep_ring && !stacked0 && plain;
+    const bool cview = !IMG && kLayer && mode == 0 && view == 0 && out.scache_mode != 1 && !keep_ring && !stacked0 && plain;
     const bool mk_cache = cview && fresh && !SM::ORDMAX;
     const bool use_cache = cview && !fresh && S.scache_ok[e] != 0;
     uint8_t *const scache = S.scache + (size_t)e * FR;
@@ -1295,7 +1301,7 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
         MG_PROF(4);
     }
     if (sm.err) { if (tid == 0) S.overflow[e] |= 4 << view; }
-    if (mode == 0 && tid == 0) S.hist_head[view * S.N + e] = nh;
+    if (!IMG && mode == 0 && tid == 0) S.hist_head[view * S.N + e] = nh;
     if (cview && fresh && tid == 0) S.scache_ok[e] = mk_cache ? 1 : 0;
     MG_PROF_END(16 * view);
 }

@@ -2,7 +2,7 @@
 // Each feature's entry points sit next to its kernels: create / seed / bind / reset / step / step_seq / getters / destroy in
 // mg_sim.hip, snapshots in mg_snapshot.hip, mg_lookahead in mg_lookahead.hip, mg_plan in mg_plan.hip, mg_plan_cem in
 // mg_cem.hip (each with its _obj form beside it), mg_plan_beam in mg_beam.hip, replay and restack in mg_replay.hip,
-// explicit scenes (mg_get_scene, mg_reset_scene) in mg_scene.hip.
+// explicit scenes (mg_get_scene, mg_reset_scene) in mg_scene.hip, imagined observations (mg_imagine) in mg_imagine.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -68,7 +68,7 @@ struct mg_sim {
     hipEvent_t ev_snap = nullptr;
     int snap_inflight = 0;
     // rollout pools (mg_plan.h), two allocations so that a lookahead on one stream and a plan on another share no
-    // memory: look holds num_envs rollouts (mg_lookahead, allocated by the first call), fan K * num_envs (mg_plan and
+    // memory: look holds num_envs rollouts (mg_lookahead and mg_imagine, allocated by the first call), fan K * num_envs (mg_plan and
     // mg_plan_cem: allocated by the first call, re-allocated by a call that needs more rollouts)
     RolloutPool look, fan;
     // optional per-kernel timing (hipEvents on the launch stream)

@@ -35,6 +35,7 @@ UNITS = {  # translation unit -> every header it includes, directly or not (one 
     "mg_step_quad.hip": _STEP,
     "mg_step_hbm.hip": _STEP,
     "mg_lookahead.hip": _SIM,
+    "mg_imagine.hip": _SIM + ["mg_imagine.h"],   # mg_imagine: segmented lookahead + frame-less render, and its stack pass
     "mg_look_v4.hip": _LOOK,
     "mg_look_quad.hip": _LOOK,
     "mg_look_hbm.hip": _LOOK,

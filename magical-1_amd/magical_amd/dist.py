@@ -324,7 +324,10 @@ class ShardedVecEnv:
     one passed in -- the gloo tests use the oracle's); 'stacked' (default on CPU tensors) all-gathers the
     whole observations.  In 'frames' mode the receivers' rings are valid only from reset_async() on:
     step_async() raises before the shard's first reset_async() and after the VecMagicalEnv underneath was
-    reset directly (vec.reset()), since the other ranks' rings would then hold stale frames of its envs."""
+    reset directly (vec.reset()), since the other ranks' rings would then hold stale frames of its envs.
+
+    There is no imagine() here: imagined observations are a per-rank call on the shard's own envs
+    (self.vec.imagine(...), plain frames only with the default window rings) and are not gathered."""
 
     def __init__(self, env_name, envs_per_rank, rank=None, device=None, base_seed=1000, gather=False, vec=None,
                  gather_mode=None, restacker=None, max_episode_steps=None, emulate_world=None, nbuf=3, window=True,

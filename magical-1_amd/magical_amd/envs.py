@@ -116,6 +116,38 @@ def seq_actions(actions, num_envs, fn, letter, device=None):
     return a.to(device=device, dtype=torch.uint8)
 
 
+def imagine_actions(actions, num_envs, every, device=None):
+    """imagine()'s arguments checked on the host: (actions as a uint8 [H, num_envs] tensor on `device`, every, F =
+    ceil(H / every)); ValueError for actions that are not integers, any other shape, H outside [1, 4096] or `every`
+    outside [1, H]."""
+    a = torch.as_tensor(actions)
+    if a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool:
+        raise ValueError(f"imagine: actions must be integer action ids, got {a.dtype}")
+    a = seq_actions(a, num_envs, "imagine", "H", device)
+    H = int(a.shape[0])
+    if not 1 <= H <= 4096:
+        raise ValueError(f"imagine: H must be in [1, 4096], got {H}")
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not 1 <= int(every) <= H:
+        raise ValueError(f"imagine: every must be an integer in [1, {H}], got {every!r}")
+    return a, int(every), -(-H // int(every))
+
+
+def imagine_layout(preproc, stacks):
+    """Which of mg_imagine_out's buffers imagine() fills for a preprocessor, and where the observation keys come from:
+    (buffer names, OrderedDict key -> buffer name).  stacks=False: the 3-channel current frames of both views.
+    stacks=True: the keys step() returns -- LoResStack's allo and ego are the stacks (built from the plain frames, which
+    are filled too), the others' past_obs is the stack of their stacked view (LoRes3EA: allo_f | three ego frames)."""
+    if preproc is None:
+        raise ValueError("imagine: the unwrapped 384^2 surface has no LoRes frame")
+    keys = collections.OrderedDict([("allo", "allo"), ("ego", "ego")])
+    if stacks:
+        if preproc == "LoResStack":
+            keys = collections.OrderedDict([("allo", "stack_allo"), ("ego", "stack_ego")])
+        else:
+            keys["past_obs"] = "stack_allo" if preproc == "LoRes4A" else "stack_ego"
+    return ["allo", "ego"] + [b for b in keys.values() if b.startswith("stack_")], keys
+
+
 def check_out(out, fn, shape, device):
     """An out= argument: `out` if it is a contiguous uint8 tensor on `device` of `shape` (an int: so many bytes in any
     shape), else ValueError."""
@@ -572,6 +604,44 @@ class VecMagicalEnv:
         zero-step lookahead."""
         return self.lookahead(torch.empty((0, self.num_envs), dtype=torch.uint8))["score"]
 
+    def imagine(self, actions, every=1, stacks=False, details=False, out=None):
+        """What the agent would SEE if these envs ran these actions -- without touching them (mg_imagine): lookahead()'s
+        rollout, rendered after every `every` env-steps.  actions: [H, N] integer action ids (tensor or array-like; [N]
+        is H = 1), 1 <= H <= 4096, 1 <= every <= H; F = ceil(H / every) frames per env.  Frame f of env e is the LoRes
+        current frame of its state after min((f + 1) * every, n) env-steps, n = min(H, steps left in its episode): the
+        bytes the f+1-th of F successive step_seq(actions[f * every:(f + 1) * every]) calls would show within the
+        episode.  An env whose episode ends inside the horizon stops there (no auto-reset) and repeats its terminal
+        frame.  Returns an OrderedDict of fresh uint8 device tensors with a leading F axis: stacks=False gives 'allo' and
+        'ego', the 3-channel current frames [F, N, 96, 96, 3]; stacks=True gives the keys step() returns for the
+        preprocessor -- LoResStack 'allo' and 'ego' [F, N, 96, 96, 12], the others 'allo', 'ego' and 'past_obs' [F, N,
+        96, 96, 12] -- where a stack holds the four newest frames up to frame f, oldest first, the env's real history
+        before frame 0 (after a terminal step the repeated frame keeps entering the stack: such stacks correspond to no
+        real step).  Channels-first preprocessors return permuted views, as step() does.  details=True adds 'score',
+        'steps' and 'errors' -- and 'bodies' and 'counts' of the final state -- bit for bit lookahead(actions,
+        bodies=True)'s (errors also carries a render capacity flag raised while drawing).
+        out: a dict of contiguous HWC uint8 tensors to fill instead, keyed like the result.  stacks=True needs the
+        env's own frame history: NativeError with window=True or frames_only outputs; plain frames work in every mode.
+        Enqueued on the current stream."""
+        a, every, F = imagine_actions(actions, self.num_envs, every, self.device)
+        bufs, keys = imagine_layout(self.spec.preproc, stacks)
+        n = self.num_envs
+        shape = {b: (F, n, 96, 96, 12 if b.startswith("stack_") else 3) for b in bufs}
+        if out is not None and not set(out) <= set(keys):
+            raise ValueError(f"imagine: out has keys {sorted(set(out) - set(keys))}, the result has {list(keys)}")
+        given = {} if out is None else {keys[k]: check_out(v, "imagine", shape[keys[k]], self.device) for k, v in out.items()}
+        mem = {b: given[b] if b in given else torch.empty(shape[b], dtype=torch.uint8, device=self.device) for b in bufs}
+        fr = native.mg_imagine_out(**{b: t.data_ptr() for b, t in mem.items()})
+        a = a.contiguous()
+        res = self._alloc([("score", (n,), torch.float64), ("steps", (n,), torch.int32), ("errors", (n,), torch.int32),
+                           ("bodies", (n, 16, 6), torch.float64), ("counts", (n, 4), torch.int32)] if details else [])
+        lo = native.mg_lookahead_out(**{k: v.data_ptr() for k, v in res.items()}) if details else None
+        native.check(self.lib.mg_imagine(self.handle, ctypes.c_void_p(a.data_ptr()), int(a.shape[0]), every,
+                                         None if lo is None else ctypes.byref(lo), ctypes.byref(fr), self._stream()))
+        self._last_imagine = a   # (alive until the next call: the kernels read it on the stream)
+        obs = collections.OrderedDict((k, mem[b].permute(0, 1, 4, 2, 3) if self._chw else mem[b]) for k, b in keys.items())
+        obs.update(res)
+        return obs
+
     # -- planning ----------------------------------------------------------------
     def plan(self, actions, details=False, objective=None):
         """Which of K candidate action sequences is best for each env -- without touching the envs (mg_plan).
@@ -833,6 +903,16 @@ class MagicalEnv:
         if trace:
             out.update(score_trace=res["score_trace"][:, 0].cpu().numpy(), reward_trace=res["reward_trace"][:, 0].cpu().numpy())
         return out
+
+    def imagine(self, actions, every=1, stacks=False):
+        """The LoRes observations the agent would see along `actions` (a sequence of 1 .. 4096 action ids, cut at the
+        episode's end, after which the terminal frame repeats) from the current state, which stays as it is: an
+        OrderedDict of uint8 arrays with a leading F = ceil(len(actions) / every) axis, keys and meaning as
+        VecMagicalEnv.imagine's for this one env."""
+        self._require_reset("imagine")
+        a = torch.as_tensor(np.asarray(actions)).reshape(-1, 1)
+        return collections.OrderedDict((k, v[:, 0].cpu().numpy())
+                                       for k, v in self._vec.imagine(a, every=every, stacks=stacks).items())
 
     def plan(self, actions, objective=None):
         """The best of K candidate action sequences from the current state, which stays as it is.  actions: [H, K]

@@ -19,7 +19,7 @@ EXPORTS = ["mg_create", "mg_bind_outputs", "mg_reset", "mg_step", "mg_render_ful
            "mg_set_episode_steps", "mg_selftest_sincos", "mg_replay_lores", "mg_restack", "mg_restack_window", "mg_bind_window",
            "mg_window_start", "mg_snapshot_bytes", "mg_snapshot", "mg_restore", "mg_lookahead", "mg_plan", "mg_plan_sample",
            "mg_plan_cem", "mg_lookahead_obj", "mg_plan_obj", "mg_plan_cem_obj", "mg_plan_beam", "mg_step_seq", "mg_get_rng",
-           "mg_selftest_mt", "mg_get_scene", "mg_reset_scene", "mg_destroy",
+           "mg_selftest_mt", "mg_get_scene", "mg_reset_scene", "mg_imagine", "mg_destroy",
            "mg_last_error"]
 PLAN_MAX_ROLLOUTS = 262144   # MG_PLAN_MAX_ROLLOUTS: K * num_envs of one mg_plan call
 OBJ_FINAL, OBJ_RETURN, OBJ_PEAK = 0, 1, 2   # MG_OBJ_*
@@ -42,6 +42,11 @@ class mg_buffers(ctypes.Structure):
 class mg_lookahead_out(ctypes.Structure):
     _fields_ = [("score", ctypes.c_void_p), ("steps", ctypes.c_void_p), ("bodies", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p), ("errors", ctypes.c_void_p)]
+
+
+class mg_imagine_out(ctypes.Structure):
+    _fields_ = [("allo", ctypes.c_void_p), ("ego", ctypes.c_void_p), ("stack_allo", ctypes.c_void_p),
+                ("stack_ego", ctypes.c_void_p)]
 
 
 class mg_plan_out(ctypes.Structure):
@@ -174,6 +179,8 @@ def load():
     if hasattr(lib, "mg_get_scene"):   # (an experiment variant built from an older tree may predate them)
         lib.mg_get_scene.argtypes = [vp, vp, vp]
         lib.mg_reset_scene.argtypes = [vp, vp, vp, i32, vp, vp]
+    if hasattr(lib, "mg_imagine"):   # (the same)
+        lib.mg_imagine.argtypes = [vp, vp, i32, i32, ctypes.POINTER(mg_lookahead_out), ctypes.POINTER(mg_imagine_out), vp]
     lib.mg_destroy.argtypes = [vp]
     lib.mg_destroy.restype = None
     lib.mg_last_error.restype = ctypes.c_char_p

@@ -24,7 +24,7 @@ import ctypes
 import torch
 
 from . import native
-from .envs import VecMagicalEnv, assemble_obs, plan_actions, scene_tensor, seq_actions
+from .envs import VecMagicalEnv, assemble_obs, imagine_actions, plan_actions, scene_tensor, seq_actions
 
 
 _SIGNED = {torch.uint16: torch.int16, torch.uint32: torch.int32}
@@ -306,6 +306,21 @@ class PipelinedVecEnv:
         a = seq_actions(actions, self.num_envs, "lookahead", "H", self.device)
         return join(self._per_chunk(lambda k, sim, lo, hi: sim.lookahead(
             a[:, lo:hi].contiguous(), bodies=bodies, objective=objective, trace=trace)), self._caller())
+
+    def imagine(self, actions, every=1, stacks=False, details=False):
+        """VecMagicalEnv.imagine for the whole pool: actions [H, num_envs] ([num_envs]: H = 1); chunk k imagines its
+        columns on its own stream and the results are joined in env order -- the frames and stacks [F, num_envs, ...]
+        along their env axis, the details as lookahead()'s.  (No out=: every chunk fills tensors of its own.)"""
+        a, every, _ = imagine_actions(actions, self.num_envs, every, self.device)
+        parts = self._per_chunk(lambda k, sim, lo, hi: sim.imagine(a[:, lo:hi].contiguous(), every=every, stacks=stacks,
+                                                                   details=details))
+        frames = [collections.OrderedDict((key, p.pop(key)) for key in ("allo", "ego", "past_obs") if key in p) for p in parts]
+        out = collections.OrderedDict((key, torch.cat([f[key] for f in frames], dim=1)) for key in frames[0])
+        for f in frames:   # (allocated on the chunks' streams, read here on the caller's: as join's parts)
+            for t in f.values():
+                t.record_stream(self._caller())
+        out.update(join(parts, self._caller()) if details else {})
+        return out
 
     def plan(self, actions, details=False, objective=None):
         """VecMagicalEnv.plan for the whole pool: actions [H, K, num_envs] ([K, num_envs]: H = 1); objective as
