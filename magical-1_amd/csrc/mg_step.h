@@ -351,10 +351,11 @@ MG_DEV void arbiter_apply(const MGState &S, int e, int slot) {
 template <int NB>
 struct RegBodies { double vx[NB], vy[NB], w[NB], vbx[NB], vby[NB], wb[NB], minv[NB], iinv[NB]; };
 
+// a joint row's pre-stepped terms (constant over the sweep: read from the LDS view) and what the row writes
 struct RegCons {
-    double r1x, r1y, r2x, r2y, k11, k12, k21, k22, bias, bias2, jacc, jacc2, jmax, ratio, ratio_inv, isum, rate, twrn,
-        wcoef;
+    double r1x, r1y, r2x, r2y, k11, k12, k21, k22, bias, bias2, jmax, ratio, ratio_inv, isum, rate, wcoef;
 };
+struct RegAcc { double jacc, jacc2, twrn; };
 
 // compile-time body slot (constraints; b < 0 = the static body)
 template <int NB>
@@ -387,41 +388,47 @@ MG_DEV void rb_store(const RegBodies<NB> &R, const MGState &S, int e) {
 }
 
 MG_DEV void rc_load(RegCons &q, const MGState &S, int e, int c, int type, double dt) {
-    q.jacc = CPA(CP_JACC, c); q.jacc2 = 0.0; q.jmax = CPA(CP_MAXF, c) * dt;
+    q = RegCons{};
+    q.jmax = CPA(CP_MAXF, c) * dt;
     q.isum = CPA(CP_ISUM, c); q.bias = CPA(CP_BIAS, c);
     if (type == MG_C_PIVOT) {
-        q.jacc2 = CPA(CP_JACC2, c); q.bias2 = CPA(CP_BIAS2, c);
+        q.bias2 = CPA(CP_BIAS2, c);
         q.r1x = CPA(CP_R1X, c); q.r1y = CPA(CP_R1Y, c); q.r2x = CPA(CP_R2X, c); q.r2y = CPA(CP_R2Y, c);
         q.k11 = CPA(CP_K11, c); q.k12 = CPA(CP_K12, c); q.k21 = CPA(CP_K21, c); q.k22 = CPA(CP_K22, c);
     }
     if (type == MG_C_GEAR) { q.ratio = CPA(CP_RATIO, c); q.ratio_inv = CPA(CP_RATIO_INV, c); }
     if (type == MG_C_MOTOR) q.rate = CPA(CP_RATE, c);
-    if (type == MG_C_SPRING) { q.twrn = CPA(CP_TWRN, c); q.wcoef = CPA(CP_WCOEF, c); }
+    if (type == MG_C_SPRING) q.wcoef = CPA(CP_WCOEF, c);
 }
-MG_DEV void rc_store(const RegCons &q, const MGState &S, int e, int c, int type) {
-    CPA(CP_JACC, c) = q.jacc;
-    if (type == MG_C_PIVOT) CPA(CP_JACC2, c) = q.jacc2;
-    if (type == MG_C_SPRING) CPA(CP_TWRN, c) = q.twrn;
+MG_DEV void ra_load(RegAcc &j, const MGState &S, int e, int c, int type) {
+    j.jacc = CPA(CP_JACC, c); j.jacc2 = 0.0; j.twrn = 0.0;
+    if (type == MG_C_PIVOT) j.jacc2 = CPA(CP_JACC2, c);
+    if (type == MG_C_SPRING) j.twrn = CPA(CP_TWRN, c);
+}
+MG_DEV void ra_store(const RegAcc &j, const MGState &S, int e, int c, int type) {
+    CPA(CP_JACC, c) = j.jacc;
+    if (type == MG_C_PIVOT) CPA(CP_JACC2, c) = j.jacc2;
+    if (type == MG_C_SPRING) CPA(CP_TWRN, c) = j.twrn;
 }
 
 template <int NB>
-MG_DEV void rcons_cached(RegBodies<NB> &R, const RegCons &q, int a, int b, int type, double dt_coef) {
+MG_DEV void rcons_cached(RegBodies<NB> &R, const RegCons &q, const RegAcc &acc, int a, int b, int type, double dt_coef) {
     switch (type) {
     case MG_C_PIVOT: {
-        V2 j = vmult(v2(q.jacc, q.jacc2), dt_coef);
+        V2 j = vmult(v2(acc.jacc, acc.jacc2), dt_coef);
         rapply(R, a, vneg(j), v2(q.r1x, q.r1y));
         rapply(R, b, j, v2(q.r2x, q.r2y));
         break;
     }
     case MG_C_GEAR: {
-        double j = q.jacc * dt_coef;
+        double j = acc.jacc * dt_coef;
         if (a >= 0) R.w[a] -= j * R.iinv[a] * q.ratio_inv;
         if (b >= 0) R.w[b] += j * R.iinv[b];
         break;
     }
     case MG_C_ROTLIMIT:
     case MG_C_MOTOR: {
-        double j = q.jacc * dt_coef;
+        double j = acc.jacc * dt_coef;
         if (a >= 0) R.w[a] -= j * R.iinv[a];
         if (b >= 0) R.w[b] += j * R.iinv[b];
         break;
@@ -431,7 +438,7 @@ MG_DEV void rcons_cached(RegBodies<NB> &R, const RegCons &q, int a, int b, int t
 }
 
 template <int NB>
-MG_DEV void rcons_apply(RegBodies<NB> &R, RegCons &q, int a, int b, int type) {
+MG_DEV void rcons_apply(RegBodies<NB> &R, const RegCons &q, RegAcc &acc, int a, int b, int type) {
     switch (type) {
     case MG_C_PIVOT: {
         V2 r1 = v2(q.r1x, q.r1y), r2 = v2(q.r2x, q.r2y);
@@ -440,9 +447,9 @@ MG_DEV void rcons_apply(RegBodies<NB> &R, RegCons &q, int a, int b, int type) {
         V2 vr = vsub(v2_, v1);
         V2 d = vsub(v2(q.bias, q.bias2), vr);
         V2 j = v2(d.x * q.k11 + d.y * q.k12, d.x * q.k21 + d.y * q.k22);
-        V2 jOld = v2(q.jacc, q.jacc2);
+        V2 jOld = v2(acc.jacc, acc.jacc2);
         V2 jAcc = vclamp(vadd(jOld, j), q.jmax);
-        q.jacc = jAcc.x; q.jacc2 = jAcc.y;
+        acc.jacc = jAcc.x; acc.jacc2 = jAcc.y;
         V2 dj = vsub(jAcc, jOld);
         rapply(R, a, vneg(dj), r1);
         rapply(R, b, dj, r2);
@@ -451,9 +458,9 @@ MG_DEV void rcons_apply(RegBodies<NB> &R, RegCons &q, int a, int b, int type) {
     case MG_C_GEAR: {
         double wr = rw(R, b) * q.ratio - rw(R, a);
         double j = (q.bias - wr) * q.isum;
-        double jOld = q.jacc;
+        double jOld = acc.jacc;
         double jAcc = cpclamp(jOld + j, -q.jmax, q.jmax);
-        q.jacc = jAcc;
+        acc.jacc = jAcc;
         j = jAcc - jOld;
         if (a >= 0) R.w[a] -= j * R.iinv[a] * q.ratio_inv;
         if (b >= 0) R.w[b] += j * R.iinv[b];
@@ -464,9 +471,9 @@ MG_DEV void rcons_apply(RegBodies<NB> &R, RegCons &q, int a, int b, int type) {
         if (!bias) return;
         double wr = rw(R, b) - rw(R, a);
         double j = -(bias + wr) * q.isum;
-        double jOld = q.jacc;
+        double jOld = acc.jacc;
         double jAcc = bias < 0.0 ? cpclamp(jOld + j, 0.0, q.jmax) : cpclamp(jOld + j, -q.jmax, 0.0);
-        q.jacc = jAcc;
+        acc.jacc = jAcc;
         j = jAcc - jOld;
         if (a >= 0) R.w[a] -= j * R.iinv[a];
         if (b >= 0) R.w[b] += j * R.iinv[b];
@@ -475,9 +482,9 @@ MG_DEV void rcons_apply(RegBodies<NB> &R, RegCons &q, int a, int b, int type) {
     case MG_C_MOTOR: {
         double wr = rw(R, b) - rw(R, a) + q.rate;
         double j = -wr * q.isum;
-        double jOld = q.jacc;
+        double jOld = acc.jacc;
         double jAcc = cpclamp(jOld + j, -q.jmax, q.jmax);
-        q.jacc = jAcc;
+        acc.jacc = jAcc;
         j = jAcc - jOld;
         if (a >= 0) R.w[a] -= j * R.iinv[a];
         if (b >= 0) R.w[b] += j * R.iinv[b];
@@ -485,10 +492,10 @@ MG_DEV void rcons_apply(RegBodies<NB> &R, RegCons &q, int a, int b, int type) {
     }
     case MG_C_SPRING: {
         double wrn = rw(R, a) - rw(R, b);
-        double w_damp = (q.twrn - wrn) * q.wcoef;
-        q.twrn = wrn + w_damp;
+        double w_damp = (acc.twrn - wrn) * q.wcoef;
+        acc.twrn = wrn + w_damp;
         double j_damp = w_damp * q.isum;
-        q.jacc += j_damp;
+        acc.jacc += j_damp;
         if (a >= 0) R.w[a] += j_damp * R.iinv[a];
         if (b >= 0) R.w[b] -= j_damp * R.iinv[b];
         break;
@@ -831,26 +838,73 @@ MG_DEV void rstatic_load(RegCons *q, const MGState &S, int e, double dt) {
     }
 }
 template <int NCS, int C = 0>
-MG_DEV void rstatic_store(const RegCons *q, const MGState &S, int e) {
+MG_DEV void rstatic_load_acc(RegAcc *acc, const MGState &S, int e) {
     if constexpr (C < NCS) {
-        rc_store(q[C], S, e, C, static_cons(C).type);
-        rstatic_store<NCS, C + 1>(q, S, e);
+        ra_load(acc[C], S, e, C, static_cons(C).type);
+        rstatic_load_acc<NCS, C + 1>(acc, S, e);
+    }
+}
+template <int NCS, int C = 0>
+MG_DEV void rstatic_store(const RegAcc *acc, const MGState &S, int e) {
+    if constexpr (C < NCS) {
+        ra_store(acc[C], S, e, C, static_cons(C).type);
+        rstatic_store<NCS, C + 1>(acc, S, e);
     }
 }
 template <int NCS, int NB, int C = 0>
-MG_DEV void rstatic_cached(RegBodies<NB> &R, const RegCons *q, double dt_coef) {
+MG_DEV void rstatic_cached(RegBodies<NB> &R, const RegCons *q, const RegAcc *acc, double dt_coef) {
     if constexpr (C < NCS) {
         constexpr ConsDesc d = static_cons(C);
-        rcons_cached(R, q[C], d.a, d.b, d.type, dt_coef);
-        rstatic_cached<NCS, NB, C + 1>(R, q, dt_coef);
+        rcons_cached(R, q[C], acc[C], d.a, d.b, d.type, dt_coef);
+        rstatic_cached<NCS, NB, C + 1>(R, q, acc, dt_coef);
     }
 }
 template <int NCS, int NB, int C = 0>
-MG_DEV void rstatic_apply(RegBodies<NB> &R, RegCons *q) {
+MG_DEV void rstatic_apply(RegBodies<NB> &R, const RegCons *q, RegAcc *acc) {
     if constexpr (C < NCS) {
         constexpr ConsDesc d = static_cons(C);
-        rcons_apply(R, q[C], d.a, d.b, d.type);
-        rstatic_apply<NCS, NB, C + 1>(R, q);
+        rcons_apply(R, q[C], acc[C], d.a, d.b, d.type);
+        rstatic_apply<NCS, NB, C + 1>(R, q, acc);
+    }
+}
+
+// The streamed sweep: a row's terms are not on the dependence chain (the body velocities are) and are constant
+// over the iterations, so instead of holding every row's for the whole sweep, row C's arrive in `cur` and row
+// C + 1's reads from the LDS view (constant offsets from the lane's column) are issued before row C's impulse is
+// computed: their latency passes beside the chain.  The last row fetches row 0's for the next pass, so `cur` holds
+// row 0's terms on entry and on return.  Only the accumulators a row writes stay in registers.
+template <int NCS, int NB, int C = 0>
+MG_DEV void rstream_cached(RegBodies<NB> &R, RegCons &cur, const RegAcc *acc, const MGState &S, int e, double dt,
+                           double dt_coef) {
+    if constexpr (C < NCS) {
+        constexpr ConsDesc d = static_cons(C);
+        constexpr int N = (C + 1) % NCS;
+        RegCons nxt;
+        rc_load(nxt, S, e, N, static_cons(N).type, dt);
+        rcons_cached(R, cur, acc[C], d.a, d.b, d.type, dt_coef);
+        cur = nxt;
+        rstream_cached<NCS, NB, C + 1>(R, cur, acc, S, e, dt, dt_coef);
+    }
+}
+// ACCW: the accumulators streamed as well (acc[0] holds the current row's; written back after the row)
+template <int NCS, int NB, bool ACCW, int C = 0>
+MG_DEV void rstream_apply(RegBodies<NB> &R, RegCons &cur, RegAcc *acc, const MGState &S, int e, double dt) {
+    if constexpr (C < NCS) {
+        constexpr ConsDesc d = static_cons(C);
+        constexpr int N = (C + 1) % NCS;
+        RegCons nxt;
+        RegAcc nacc;
+        rc_load(nxt, S, e, N, static_cons(N).type, dt);
+        if constexpr (ACCW) {
+            ra_load(nacc, S, e, N, static_cons(N).type);
+            rcons_apply(R, cur, acc[0], d.a, d.b, d.type);
+            ra_store(acc[0], S, e, C, d.type);
+            acc[0] = nacc;
+        } else {
+            rcons_apply(R, cur, acc[C], d.a, d.b, d.type);
+        }
+        cur = nxt;
+        rstream_apply<NCS, NB, ACCW, C + 1>(R, cur, acc, S, e, dt);
     }
 }
 
@@ -860,15 +914,21 @@ __host__ __device__ constexpr int static_nbodies(int ncs) { return ncs > 10 ? 7 
 // applyCachedImpulse + 10 iterations of the LDS variants, register-resident; NARB arbiters in registers (the
 // 8-env form: 1 -- MoveToRegion 0.414 -> 0.392 ms, MoveToCorner 0.757 -> 0.740 ms per 2048-env chunk; 2 made
 // the MoveToCorner form spill and measured slower, and the 16-env forms spill already at 1: 0 there)
-template <int NCS, int NARB>
+// STREAM (quad_stream, mg_stepq.h): 0 the joint rows' terms held in registers (rstatic_*), 1 streamed from the LDS
+// view (rstream_*), 2 the rows' accumulators streamed as well
+template <int NCS, int NARB, int STREAM>
 MG_DEV void static_solve(const MGState &S, int e, double dt, double dt_coef, int nact, MGProf &P) {
     constexpr int NB = static_nbodies(NCS);
     RegBodies<NB> R;
-    RegCons q[NCS];
+    RegCons q[STREAM ? 1 : NCS];
+    RegAcc acc[NCS];
     rb_load(R, S, e);
-    rstatic_load<NCS>(q, S, e, dt);
+    if constexpr (STREAM) rc_load(q[0], S, e, 0, static_cons(0).type, dt);
+    else rstatic_load<NCS>(q, S, e, dt);
+    rstatic_load_acc<NCS>(acc, S, e);
     for (int i = 0; i < nact; i++) harb_cached_row(R, S, e, AT(S.active, i), dt_coef);
-    rstatic_cached<NCS>(R, q, dt_coef);
+    if constexpr (STREAM) rstream_cached<NCS>(R, q[0], acc, S, e, dt, dt_coef);
+    else rstatic_cached<NCS>(R, q, acc, dt_coef);
     MG_PP(P, 5);
     // the first NARB arbiters in registers when their pairs are compile-time ones (the rest through LDS)
     RegArb ra[NARB > 0 ? NARB : 1];
@@ -894,7 +954,9 @@ MG_DEV void static_solve(const MGState &S, int e, double dt, double dt_coef, int
                 if (i < nreg) rarb_row(R, ra[i]);
         }
         for (int i = nreg; i < nact; i++) harb_row(R, S, e, AT(S.active, i));
-        rstatic_apply<NCS>(R, q);
+        if constexpr (STREAM == 2) rstream_apply<NCS, NB, true>(R, q[0], acc, S, e, dt);
+        else if constexpr (STREAM) rstream_apply<NCS, NB, false>(R, q[0], acc, S, e, dt);
+        else rstatic_apply<NCS>(R, q, acc);
     }
     if constexpr (NARB > 0) {
 #pragma unroll
@@ -902,7 +964,7 @@ MG_DEV void static_solve(const MGState &S, int e, double dt, double dt_coef, int
             if (i < nreg) rarb_store(ra[i], S, e, AT(S.active, i));
     }
     rb_store(R, S, e);
-    rstatic_store<NCS>(q, S, e);
+    if constexpr (STREAM != 2) rstatic_store<NCS>(acc, S, e);
 }
 
 // ---- cpSpaceStep -----------------------------------------------------------

@@ -19,6 +19,13 @@
 #pragma once
 #include "mg_step.h"
 
+// static_solve's STREAM of a quad form.  8 lanes per env (the forms the pipelined pool runs beside the other chunks'
+// renders): the joint rows' terms streamed, so the step wavefront leaves room on its SIMD for two 72-register render
+// wavefronts -- form 5 with the accumulators resident (360 registers), form 6, with two more rows and a seventh body,
+// with the accumulators streamed as well (362; resident: 390).  4 lanes per env keep the held rows: those forms fill
+// the register file either way.
+__host__ __device__ constexpr int quad_stream(int ncs, int ql) { return ql < 8 ? 0 : ncs > 10 ? 2 : 1; }
+
 // Lane layout: env ev (0 .. 64/QL - 1) of the wavefront owns lanes ev * QL .. ev * QL + QL - 1 (a layout with
 // the serial sub-lane-0 lanes packed first in the wave measured the same, round 4: FP64 instructions cost the
 // same whatever the number of active lanes -- tools/ubench/exec_f64.hip)
@@ -203,7 +210,8 @@ MG_DEV void space_step_quad(const MGState &S, const mg_library *L, int e, int su
     MG_PP(P, 4);
     // velocity integration is the identity here (no gravity, damping 1, no forces)
     const double dt_coef = (prev_dt == 0.0 ? 0.0 : dt / prev_dt);
-    if (sub == 0) static_solve<NCS, (QL >= 8 ? 1 : 0)>(S, e, dt, dt_coef, nact, P);   // NARB: see static_solve
+    // NARB, STREAM: see static_solve
+    if (sub == 0) static_solve<NCS, (QL >= 8 ? 1 : 0), quad_stream(NCS, QL)>(S, e, dt, dt_coef, nact, P);
     MG_PP(P, 6);
 }
 
