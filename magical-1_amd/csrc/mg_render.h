@@ -484,6 +484,29 @@ MG_DEV void entity_xform(const MGState &S, int e, int ent, int x, double *xf) {
 template <class SM>
 MG_DEV int xf_slot(int ent, int x) { return x == MG_XF_MAIN ? ent : SM::RG_MAXE + x - 1; }
 
+// ---- 4x4 blocks from coverage masks (small class, LoRes modes: render_kernel, kMask) ----
+// A block's 16 pixels are the bits 4 * row + column of a mask.  A band-list slot covers one x-run [l, r1) of a row, so
+// the row's 4 bits are 2^b - 2^a with a, b the run's ends clamped to the block's columns [x0, x0 + 4] and taken from
+// x0: the same predicate l <= x < r1 for 4 consecutive x at once, on the packed int16 pair (l, r1).  An empty row
+// (l = r1 = RG_EMPTY) clamps to a = b = 4: no bit.
+typedef short rg_s16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short rg_u16x2 __attribute__((ext_vector_type(2)));
+MG_DEV uint32_t row_cover(uint32_t span, rg_s16x2 X0) {
+    const rg_s16x2 four = {4, 4};
+    rg_s16x2 p = __builtin_bit_cast(rg_s16x2, span);
+    p = __builtin_elementwise_min(__builtin_elementwise_max(p, X0) - X0, four);   // (no int16 overflow: p >= X0 first)
+    const rg_u16x2 one = {1, 1};
+    const rg_u16x2 q = one << __builtin_bit_cast(rg_u16x2, p);
+    return (uint32_t)q.y - (uint32_t)q.x;
+}
+// bit k of the 8 nibbles of w (two rows of the 4-bit outline layer) -> 8 contiguous bits
+MG_DEV uint32_t nibble_plane(uint32_t w, int k) {
+    uint32_t x = (w >> k) & 0x11111111u;
+    x = (x | (x >> 3)) & 0x03030303u;
+    x = (x | (x >> 6)) & 0x000F000Fu;
+    return (x | (x >> 12)) & 0xFFu;
+}
+
 // One (env, view) per workgroup.  MODE 0: LoRes outputs; 1: full-resolution frames; 2: LoRes outputs with the
 // stacked views as window rings (RenderOut::wring) -- its own instantiation, so the materialising kernels carry
 // none of its code (a shared build measured 4% slower render kernels, round 5).  MODE 3 (mg_imagine): the plain current
@@ -509,6 +532,8 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     constexpr int RG_CPF0 = RG_THREADS - RG_BANDLO16 < 128 ? RG_THREADS - RG_BANDLO16 : 128;
     constexpr int mode = (MODE == 2 || MODE == 3) ? 0 : MODE;
     constexpr bool WIN = MODE == 2, IMG = MODE == 3;
+    // 4-bit outline layer and LoRes output: blocks resolved from coverage masks (band spans kept as (l, r + 1))
+    constexpr bool kMask = RG_SPANW && RG_OFS && !SM::ORDMAX && SM::MPW == 8 && mode == 0;
     const int e = blockIdx.x, view = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     if (e >= S.n_envs || (out.mask && !out.mask[e])) return;
     if constexpr (IMG)
@@ -661,6 +686,26 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     if (tid < 64) wave_exclusive_scan(sm.g_nv, sm.g_voff, G, lane);
     MG_PROF(11);
     // ---- 2. per-geom matrix: view @ T_last @ ... @ T_first (Geom.render stack) ----
+    // (robot-scene class: one thread per (geom, matrix row) -- a row of a product depends on that row of the left
+    // factor alone, so the two rows kept are the same doubles, at a third of the registers of the whole products)
+    constexpr bool kRowXf = SM::MPW == 8 && 2 * SM::RG_MAXG <= RG_THREADS;
+    if constexpr (kRowXf) {
+        const int g = tid >> 1, i = tid & 1;
+        if (g < G) {
+            const mg_rpoly &rp = L->rpoly[sm.u.pre.g_rpoly[g]];
+            const int ent = sm.g_ent[g];
+            double m0 = sm.u.pre.view[3 * i], m1 = sm.u.pre.view[3 * i + 1], m2 = sm.u.pre.view[3 * i + 2];
+            for (int k = rp.nxf - 1; k >= 0; k--) {
+                const int x = rp.xf[k];
+                const double *T = x >= MG_XF_STATIC0 ? L->static_xf[x - MG_XF_STATIC0] : sm.u.pre.e_xf[xf_slot<SM>(ent, x)];
+                double t[3];
+#pragma unroll
+                for (int j = 0; j < 3; j++) t[j] = __fma_rn(m2, T[6 + j], __fma_rn(m1, T[3 + j], m0 * T[j]));   // mg_mat3_mul's row
+                m0 = t[0]; m1 = t[1]; m2 = t[2];
+            }
+            sm.u.pre.g_m[g][3 * i] = m0; sm.u.pre.g_m[g][3 * i + 1] = m1; sm.u.pre.g_m[g][3 * i + 2] = m2;
+        }
+    } else
     for (int g = tid; g < G; g += RG_THREADS) {
         const mg_rpoly &rp = L->rpoly[sm.u.pre.g_rpoly[g]];
         int ent = sm.g_ent[g];
@@ -887,7 +932,6 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
     const bool mk_cache = cview && fresh && !SM::ORDMAX;
     const bool use_cache = cview && !fresh && S.scache_ok[e] != 0;
     uint8_t *const scache = S.scache + (size_t)e * FR;
-    uint4 cpf = make_uint4(0, 0, 0, 0);   // wave 2, lanes 0-35: the next band's static-layer rows
     uint8_t *o_plain = view == 0 ? out.obs_allo : out.obs_ego;
     uint8_t *o_stack = pp == MG_PREPROC_LORESSTACK ? o_plain : out.obs_past;
     // 4x4 block of this thread: wave w covers block columns [32w, 32w + 32) of both block rows, so a
@@ -903,6 +947,8 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
 #endif
     // prefetch frames t-3..t-1 of this thread's 4 pixels of band y0 (ring slots nh+1..nh+3, never
     // written this step): 3 dwords per frame
+    // (a view with the static layer has no stack: the next band's static-layer rows, prefetched by wave 2's lanes
+    // 0-35, share the first four of these registers -- cview excludes stacked0)
     uint32_t pf[3][3];
     auto prefetch = [&](int y0) {
 #pragma unroll
@@ -971,8 +1017,10 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
         b1 = y0 <= y1 ? y1 / RG_BAND + 1 : 0;
     };
     auto cache_prefetch = [&](int y0) {
-        if (use_cache && tid >= RG_CPF0 && tid < RG_CPF0 + RG_BANDLO16)
-            cpf = *(const uint4 *)(scache + (size_t)(y0 / 4) * RG_LOROW + 16 * (tid - RG_CPF0));
+        if (use_cache && tid >= RG_CPF0 && tid < RG_CPF0 + RG_BANDLO16) {
+            const uint4 t = *(const uint4 *)(scache + (size_t)(y0 / 4) * RG_LOROW + 16 * (tid - RG_CPF0));
+            pf[0][0] = t.x; pf[0][1] = t.y; pf[0][2] = t.z; pf[1][0] = t.w;
+        }
     };
     // band 0 prologue: outline layer cleared (it overlays the setup scratch: after the binning's
     // counters are done with), band list, prefetch (later bands: in the previous band's tail)
@@ -1026,7 +1074,7 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
         const uint32_t *dmb = sm.dmask[band_i & 1];
         const bool sband = use_cache && __builtin_amdgcn_readfirstlane(dmb[0] | dmb[1] | dmb[2]) == 0u;
         if (use_cache && tid >= RG_CPF0 && tid < RG_CPF0 + RG_BANDLO16)
-            sm.u.post.lo[tid - RG_CPF0] = out.scache_mode == 2 ? make_uint4(0x55555555u, 0x55555555u, 0x55555555u, 0x55555555u) : cpf;
+            sm.u.post.lo[tid - RG_CPF0] = out.scache_mode == 2 ? make_uint4(0x55555555u, 0x55555555u, 0x55555555u, 0x55555555u) : make_uint4(pf[0][0], pf[0][1], pf[0][2], pf[1][0]);
         // (wave 1; the outline items run on waves 0 and 2 at the same time)
         const bool fwave = tid >= 64 && tid < 128;
         const int lt = tid < 64 ? tid : tid - 64;   // outline-item thread index (waves 0, 2)
@@ -1068,6 +1116,9 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
                 const uint32_t v = *sp;
                 const int sa = (int16_t)(v & 0xFFFF), sb = (int16_t)(v >> 16);
                 const int l = sa < sb ? sa : sb, rr = sa < sb ? sb : sa;
+                if constexpr (kMask)   // (l, r + 1) as int16 halves; empty: both RG_EMPTY
+                    *sp = rr == RG_EMPTY ? ((uint32_t)RG_EMPTY | ((uint32_t)RG_EMPTY << 16)) : ((uint32_t)(uint16_t)l | ((uint32_t)(uint16_t)(rr + 1) << 16));
+                else
                 *sp = rr == RG_EMPTY ? (uint32_t)RG_EMPTY : ((uint32_t)(uint16_t)l | ((uint32_t)min(rr - l, 0xFFFF) << 16));
             }
         }
@@ -1117,12 +1168,101 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
         uint8_t *lo8 = (uint8_t *)sm.u.post.lo;
         MG_PROF_MARK(t_fill);
         const bool need = !use_cache || ((dmb[ox >> 5] >> (ox & 31)) & 1u);
+        // coverage-mask resolve: lane i of each wavefront holds band-list slot i -- its geom, x range, fill colour --
+        // and the wavefront the set of slots that meet its 128 pixel columns (all of them / those of the body-less
+        // entities), so the slot walk below reads them lane to scalar with no LDS round trip per slot
+        uint32_t sl_a = 0u, sl_c = 0u;   // xmin | xmax << 9 | geom << 18 (a listed geom has 0 <= xmin <= xmax < 384); R | G << 8 | B << 16
+        uint64_t wslots = 0ull, wslots_s = 0ull;
+        if constexpr (kMask) {
+            static_assert(SM::RG_MAXG <= 64 && MG_RES <= 512, "one lane per band-list slot, 9-bit columns");
+            const int wx0 = 128 * (tid >> 6);
+            bool ov = false, st = false;
+            if (lane < nbl && !(dskip & 2)) {
+                const uint32_t xr = sm.bxr[lane];
+                const int g = sm.blist[lane];
+                const uint2 cc = *(const uint2 *)&sm.col[2 * g + 1];
+                sl_a = (xr & 0x1FFu) | ((xr >> 16) << 9) | ((uint32_t)g << 18);
+                sl_c = (cc.x & 0xFFu) | ((cc.x >> 16) << 8) | (cc.y << 16);
+                ov = (int)(xr >> 16) >= wx0 && (int)(xr & 0xFFFF) <= wx0 + 127;
+                st = ov && ((sm.smask >> sm.g_ent[g]) & 1u);
+            }
+            wslots = __ballot(ov);
+            wslots_s = mk_cache ? __ballot(st) : 0ull;
+        }
         // pass 0: the frame (skipped where the static layer stands); pass 1 (the episode's first allo frame):
         // the static layer, the body-less entities alone
         auto resolve = [&](auto sonly_c, int oy) {
             constexpr bool sonly = decltype(sonly_c)::value;
             const int yb = 4 * oy, ya = y0 + yb, lpix = oy * MG_LORES + ox;
             uint32_t o[4][4];
+            uint64_t sum = 0;
+            if constexpr (kMask) {
+                // Coverage masks: bit 4 * row + column per pixel.  The slots are walked in reverse draw order
+                // (slot, geom and x range are the wavefront's: scalar control flow) and each claims what it
+                // covers of the block's still unclaimed pixels -- the pixels it wins under "later fill wins" -- until
+                // no pixel of the wavefront's blocks is left.  The outline of entity k (ordinal 2 g + 2 of its
+                // outlined geom g, bit k of a pixel's nibble) claims its pixels between the fills of g + 1 and g: the
+                // max of fill and outline ordinals, the entities taken from the highest down as the highest bit of a
+                // nibble wins.  The block's sum is then count x colour per claimant, the background for the rest.
+                // (the entities' outline ordinals, oord1[1..], are read here as 16 bits each of an SGPR pair: held
+                // across the band loop they cost the kernel spilled registers)
+                static_assert(SM::RG_MAXE <= 4 && ((2 * SM::RG_MAXG + 2) << RG_OSH) < 0x10000, "4 outline ordinals of 16 bits");
+                uint32_t eolo = 0, eohi = 0;
+#pragma unroll
+                for (int k = 0; k < SM::RG_MAXE; k++) {
+                    const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)sm.oord1[k + 1]) << (16 * (k & 1));
+                    if (k < 2) eolo |= v; else eohi |= v;
+                }
+                const uint64_t eo64 = (uint64_t)eolo | ((uint64_t)eohi << 32);
+                uint32_t wa = 0u, wb = 0u;   // outline nibbles of rows 0-1 / 2-3
+                if (!(dskip & 32)) {
+                    constexpr int RS = 2 * (MG_RES / SM::MPW);   // 16-bit halves (4 pixels) per layer row
+                    const uint16_t *bh = (const uint16_t *)&sm.u.post.band[yb][0] + ox;
+                    wa = (uint32_t)bh[0] | ((uint32_t)bh[RS] << 16);
+                    wb = (uint32_t)bh[2 * RS] | ((uint32_t)bh[3 * RS] << 16);
+                    if constexpr (sonly) { const uint32_t m = sm.smask * 0x11111111u; wa &= m; wb &= m; }
+                }
+                const bool wany = (wa | wb) != 0u;
+                const rg_s16x2 X0 = {(short)x0, (short)x0};
+                uint32_t un = 0xFFFFu, slo = 0u, shi = 0u;   // unclaimed pixels; R | G << 16 and B sums
+                auto claim = [&](uint32_t cover, uint32_t cofs) {
+                    const uint32_t c = cover & un;
+                    const uint2 cc = *(const uint2 *)((const char *)sm.col + cofs);
+                    const uint32_t n = (uint32_t)__popc(c);
+                    un ^= c;
+                    slo += __umul24(n, cc.x); shi += __umul24(n, cc.y);
+                };
+                int ek = SM::RG_MAXE - 1;   // next entity outline to place, from the last drawn down
+                auto outlines_above = [&](uint32_t ford) {   // the outlines drawn after the fill of ordinal ford
+                    while (ek >= 0) {
+                        const uint32_t eo = (uint32_t)(eo64 >> (16 * ek)) & 0xFFFFu;
+                        if (eo != 0u && eo < ford) break;
+                        if (eo != 0u && wany) claim(nibble_plane(wa, ek) | (nibble_plane(wb, ek) << 8), eo);
+                        ek--;
+                    }
+                };
+                for (uint64_t rem = sonly ? wslots_s : wslots; rem != 0ull;) {
+                    if (__ballot(un != 0u) == 0ull) break;
+                    const int slot = 63 - __builtin_clzll(rem);
+                    rem &= ~(1ull << slot);
+                    const uint32_t sa = (uint32_t)__builtin_amdgcn_readlane((int)sl_a, slot);
+                    const uint32_t sc = (uint32_t)__builtin_amdgcn_readlane((int)sl_c, slot);
+                    const uint32_t ford = (2 * (sa >> 18) + 1) << RG_OSH;
+                    outlines_above(ford);
+                    const int xmin = (int)(sa & 0x1FFu), xmax = (int)((sa >> 9) & 0x1FFu);
+                    if (xmax < x0 || xmin > x0 + 3 || un == 0u) continue;
+                    const uint4 s4 = *(const uint4 *)&sm.bspan[slot][yb];
+                    const uint32_t c = (row_cover(s4.x, X0) | (row_cover(s4.y, X0) << 4) | (row_cover(s4.z, X0) << 8) |
+                                        (row_cover(s4.w, X0) << 12)) & un;
+                    const uint32_t n = (uint32_t)__popc(c);
+                    un ^= c;
+                    slo += __umul24(n, (sc & 0xFFu) | ((sc & 0xFF00u) << 8));
+                    shi += __umul24(n, sc >> 16);
+                }
+                if (__ballot(un != 0u && wany) != 0ull) outlines_above(0u);
+                claim(un, 0u);   // background: ordinal 0
+                sum = (uint64_t)slo | ((uint64_t)shi << 32);
+            } else {
 #pragma unroll
             for (int r = 0; r < 4; r++)
 #pragma unroll
@@ -1186,11 +1326,11 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
             }
             // area sum of the block's 16 colours (a one-lookup path for blocks of one ordinal measured 2% slower:
             // the 15 compares cost more than the 16 LDS reads they save)
-            uint64_t sum = 0;
 #pragma unroll
             for (int r = 0; r < 4; r++)
 #pragma unroll
                 for (int c = 0; c < 4; c++) sum += *(const uint64_t *)((const char *)sm.col + (o[r][c] << (3 - RG_OSH)));
+            }
             if (mode == 1) {
                 for (int r = 0; r < 4; r++) {
                     uint8_t *dst = out.full + ((((size_t)e * 2 + view) * MG_RES + y0 + yb + r) * MG_RES + x0) * 3;
@@ -1237,8 +1377,10 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
         // next band's empty spans, cleared outline layer, band list (wave 2) and prefetch
         for (int i = tid; i < nbl * RG_BAND; i += RG_THREADS)
             (&sm.bspan[0][0])[i] = (uint32_t)RG_EMPTY | ((uint32_t)RG_EMPTY << 16);
+        uint32_t zero = 0u;
+        if constexpr (kMask) asm volatile("" : "+v"(zero));   // formed here: hoisted out of the band loop, the zeros were spilled
         for (int i = tid; i < ((dskip & 128) ? 0 : (int)(sizeof(sm.u.post.band) / 16)); i += RG_THREADS)
-            ((uint4 *)&sm.u.post.band[0][0])[i] = make_uint4(0, 0, 0, 0);
+            ((uint4 *)&sm.u.post.band[0][0])[i] = make_uint4(zero, zero, zero, zero);
         if (tid == 0) sm.nlong = 0;
         if (mode == 0 && !(dskip & 4)) {
             if (tid >= RG_RING0) {
@@ -1286,7 +1428,9 @@ render_kernel(MGState S, const mg_library *__restrict__ L, RenderOut out) {
                     const uint32_t byte = (f[k][sb / 4] >> (8 * (sb % 4))) & 255u;
                     if (b % 4 == 0) o[b / 4] = byte; else o[b / 4] |= byte << (8 * (b % 4));
                 }
-                uint4 *dst = (uint4 *)(o_stack + (size_t)e * FR * 4 + lrow * 4) + 3 * tid;
+                int st = tid;
+                if constexpr (kMask) asm volatile("" : "+v"(st));   // the address formed here: held across the band loop it was spilled
+                uint4 *dst = (uint4 *)(o_stack + (size_t)e * FR * 4 + lrow * 4) + 3 * st;
                 dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
                 dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
                 dst[2] = make_uint4(o[8], o[9], o[10], o[11]);
