@@ -5,6 +5,7 @@
 #pragma once
 #include "mg_phys.h"
 #include "mg_prof.h"
+#include "mg_rows.h"
 
 // ---- body access with the static body as zeros --------------------------
 struct BodyR { int b; double minv, iinv; };
@@ -14,11 +15,6 @@ MG_DEV BodyR bodyr(const MGState &S, int e, int b) {
 }
 MG_DEV V2 bv(const MGState &S, int e, int b) { return b < 0 ? v2(0.0, 0.0) : v2(AT(S.bvx, b), AT(S.bvy, b)); }
 MG_DEV double bwv(const MGState &S, int e, int b) { return b < 0 ? 0.0 : AT(S.bw, b); }
-MG_DEV V2 bvb(const MGState &S, int e, int b) { return b < 0 ? v2(0.0, 0.0) : v2(AT(S.bvbx, b), AT(S.bvby, b)); }
-MG_DEV double bwb(const MGState &S, int e, int b) { return b < 0 ? 0.0 : AT(S.bwb, b); }
-MG_DEV V2 bp(const MGState &S, int e, int b) { return b < 0 ? v2(0.0, 0.0) : v2(AT(S.bpx, b), AT(S.bpy, b)); }
-MG_DEV double ban(const MGState &S, int e, int b) { return b < 0 ? 0.0 : AT(S.ba, b); }
-
 MG_DEV void apply_impulse(const MGState &S, int e, const BodyR &B, V2 j, V2 r) {
     if (B.b < 0) return;
     AT(S.bvx, B.b) = AT(S.bvx, B.b) + j.x * B.minv;
@@ -29,17 +25,28 @@ MG_DEV void apply_impulses(const MGState &S, int e, const BodyR &A, const BodyR 
     apply_impulse(S, e, A, vneg(j), r1);
     apply_impulse(S, e, B, j, r2);
 }
-MG_DEV void apply_bias_impulse(const MGState &S, int e, const BodyR &B, V2 j, V2 r) {
-    if (B.b < 0) return;
-    AT(S.bvbx, B.b) = AT(S.bvbx, B.b) + j.x * B.minv;
-    AT(S.bvby, B.b) = AT(S.bvby, B.b) + j.y * B.minv;
-    AT(S.bwb, B.b) += B.iinv * vcross(r, j);
-}
 MG_DEV V2 relative_velocity(const MGState &S, int e, int a, int b, V2 r1, V2 r2) {
     V2 v1 = vadd(bv(S, e, a), vmult(vperp(r1), bwv(S, e, a)));
     V2 v2_ = vadd(bv(S, e, b), vmult(vperp(r2), bwv(S, e, b)));
     return vsub(v2_, v1);
 }
+// body b as one side of a solver row (mg_rows.h); the static body's side is zeros and is never stored
+MG_DEV Side side_load(const MGState &S, int e, int b) {
+    if (b < 0) return Side{};
+    return {AT(S.bvx, b), AT(S.bvy, b), AT(S.bw, b), AT(S.bvbx, b), AT(S.bvby, b), AT(S.bwb, b),
+            AT(S.bminv, b), AT(S.biinv, b)};
+}
+MG_DEV void side_store(const MGState &S, int e, int b, const Side &x) {
+    if (b < 0) return;
+    AT(S.bvx, b) = x.vx; AT(S.bvy, b) = x.vy; AT(S.bw, b) = x.w;
+}
+MG_DEV void side_store_bias(const MGState &S, int e, int b, const Side &x) {
+    if (b < 0) return;
+    AT(S.bvbx, b) = x.vbx; AT(S.bvby, b) = x.vby; AT(S.bwb, b) = x.wb;
+}
+MG_DEV V2 bp(const MGState &S, int e, int b) { return b < 0 ? v2(0.0, 0.0) : v2(AT(S.bpx, b), AT(S.bpy, b)); }
+MG_DEV double ban(const MGState &S, int e, int b) { return b < 0 ? 0.0 : AT(S.ba, b); }
+
 MG_DEV double k_scalar_body(const BodyR &B, V2 r, V2 n) {
     double rcn = vcross(r, n);
     return B.minv + B.iinv * rcn * rcn;
@@ -107,6 +114,33 @@ MG_DEV void cons_prestep_impl(const MGState &S, int e, int c, int a, int b, int 
     }
 }
 
+// a joint row's terms and accumulators (RegCons / RegAcc, mg_rows.h) from the state's constraint table
+MG_DEV void rc_load(RegCons &q, const MGState &S, int e, int c, int type, double dt) {
+    q = RegCons{};
+    q.jmax = CPA(CP_MAXF, c) * dt;
+    q.isum = CPA(CP_ISUM, c); q.bias = CPA(CP_BIAS, c);
+    if (type == MG_C_PIVOT) {
+        q.bias2 = CPA(CP_BIAS2, c);
+        q.r1x = CPA(CP_R1X, c); q.r1y = CPA(CP_R1Y, c); q.r2x = CPA(CP_R2X, c); q.r2y = CPA(CP_R2Y, c);
+        q.k11 = CPA(CP_K11, c); q.k12 = CPA(CP_K12, c); q.k21 = CPA(CP_K21, c); q.k22 = CPA(CP_K22, c);
+    }
+    if (type == MG_C_GEAR) { q.ratio = CPA(CP_RATIO, c); q.ratio_inv = CPA(CP_RATIO_INV, c); }
+    if (type == MG_C_MOTOR) q.rate = CPA(CP_RATE, c);
+    if (type == MG_C_SPRING) q.wcoef = CPA(CP_WCOEF, c);
+}
+MG_DEV void ra_load(RegAcc &j, const MGState &S, int e, int c, int type) {
+    j.jacc = CPA(CP_JACC, c); j.jacc2 = 0.0; j.twrn = 0.0;
+    if (type == MG_C_PIVOT) j.jacc2 = CPA(CP_JACC2, c);
+    if (type == MG_C_SPRING) j.twrn = CPA(CP_TWRN, c);
+}
+MG_DEV void ra_store(const RegAcc &j, const MGState &S, int e, int c, int type) {
+    CPA(CP_JACC, c) = j.jacc;
+    if (type == MG_C_PIVOT) CPA(CP_JACC2, c) = j.jacc2;
+    if (type == MG_C_SPRING) CPA(CP_TWRN, c) = j.twrn;
+}
+
+// form 0 keeps its own text of joint_row / joint_cached (mg_rows.h; edit them in step): on the shared rows every
+// form-0 kernel took 16 more scratch bytes per lane ("Shared solver rows")
 MG_DEV void cons_cached_impl(const MGState &S, int e, int c, int a, int b, int type, double dt_coef) {
     BodyR A = bodyr(S, e, a), B = bodyr(S, e, b);
     switch (type) {
@@ -295,79 +329,67 @@ MG_DEV void arbiter_prestep(const MGState &S, const mg_library *L, int e, int sl
     }
 }
 
+// contact k of an arbiter slot: its pre-stepped terms and accumulated impulses (ContactTerms / ContactAcc, mg_rows.h)
+MG_DEV ContactTerms acon_terms(const MGState &S, int e, int slot, int k) {
+    return {ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot), ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot),
+            ACON(k, AC_NMASS, slot), ACON(k, AC_TMASS, slot), ACON(k, AC_BIAS, slot)};
+}
+MG_DEV ContactAcc acon_acc(const MGState &S, int e, int slot, int k) {
+    return {ACON(k, AC_JB, slot), ACON(k, AC_JN, slot), ACON(k, AC_JT, slot)};
+}
+MG_DEV void acon_acc_store(const MGState &S, int e, int slot, int k, const ContactAcc &acc) {
+    ACON(k, AC_JB, slot) = acc.jb; ACON(k, AC_JN, slot) = acc.jn; ACON(k, AC_JT, slot) = acc.jt;
+}
+
 MG_DEV void arbiter_cached(const MGState &S, int e, int slot, double dt_coef) {
     if (AT(S.astate, slot) == ARB_FIRST) return;
     int a = AT(S.asa, slot), b = AT(S.asb, slot);
-    BodyR A = bodyr(S, e, a), B = bodyr(S, e, b);
+    Side A = side_load(S, e, a), B = side_load(S, e, b);
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     int cnt = AT(S.acount, slot);
-    for (int k = 0; k < cnt; k++) {
-        V2 j = vrotate(n, v2(ACON(k, AC_JN, slot), ACON(k, AC_JT, slot)));
-        apply_impulses(S, e, A, B, v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)),
-                       v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot)), vmult(j, dt_coef));
-    }
+    for (int k = 0; k < cnt; k++)
+        contact_cached<true, true>(A, B, acon_terms(S, e, slot, k), acon_acc(S, e, slot, k), n, dt_coef);
+    side_store(S, e, a, A);
+    side_store(S, e, b, B);
 }
 
 MG_DEV void arbiter_apply(const MGState &S, int e, int slot) {
     int a = AT(S.asa, slot), b = AT(S.asb, slot);
-    BodyR A = bodyr(S, e, a), B = bodyr(S, e, b);
+    Side A = side_load(S, e, a), B = side_load(S, e, b);
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     double friction = AT(S.au, slot);
     int cnt = AT(S.acount, slot);
     for (int k = 0; k < cnt; k++) {
-        double nMass = ACON(k, AC_NMASS, slot);
-        V2 r1 = v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)), r2 = v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot));
-        V2 vb1 = vadd(bvb(S, e, a), vmult(vperp(r1), bwb(S, e, a)));
-        V2 vb2 = vadd(bvb(S, e, b), vmult(vperp(r2), bwb(S, e, b)));
-        V2 vr = relative_velocity(S, e, a, b, r1, r2);
-        double vbn = vdot(vsub(vb2, vb1), n);
-        double vrn = vdot(vr, n);
-        double vrt = vdot(vr, vperp(n));
-        double jbn = (ACON(k, AC_BIAS, slot) - vbn) * nMass;
-        double jbnOld = ACON(k, AC_JB, slot);
-        double jBias = cpmax(jbnOld + jbn, 0.0);
-        ACON(k, AC_JB, slot) = jBias;
-        double jn = -(0.0 + vrn) * nMass;
-        double jnOld = ACON(k, AC_JN, slot);
-        double jnAcc = cpmax(jnOld + jn, 0.0);
-        ACON(k, AC_JN, slot) = jnAcc;
-        double jtMax = friction * jnAcc;
-        double jt = -vrt * ACON(k, AC_TMASS, slot);
-        double jtOld = ACON(k, AC_JT, slot);
-        double jtAcc = cpclamp(jtOld + jt, -jtMax, jtMax);
-        ACON(k, AC_JT, slot) = jtAcc;
-        V2 jb = vmult(n, jBias - jbnOld);
-        apply_bias_impulse(S, e, A, vneg(jb), r1);
-        apply_bias_impulse(S, e, B, jb, r2);
-        apply_impulses(S, e, A, B, r1, r2, vrotate(n, v2(jnAcc - jnOld, jtAcc - jtOld)));
+        ContactAcc acc = acon_acc(S, e, slot, k);
+        contact_row<true, true>(A, B, acon_terms(S, e, slot, k), acc, n, friction);
+        acon_acc_store(S, e, slot, k, acc);
     }
+    side_store(S, e, a, A);
+    side_store(S, e, b, B);
+    side_store_bias(S, e, a, A);
+    side_store_bias(S, e, b, B);
 }
 
 // ---- register-resident solver sweep (LDS variants) -----------------------
 // With the constraint list known at compile time, applyCachedImpulse and the 10 solver
 // iterations run on body velocities and constraint terms held in VGPRs: constraints index
-// bodies by constants, arbiters (runtime body slots) through select chains.  Same operations
-// in the same order as cons_cached_impl / cons_apply_impl / arbiter_cached / arbiter_apply.
+// bodies by constants, arbiters (runtime body slots) through select chains.
 template <int NB>
 struct RegBodies { double vx[NB], vy[NB], w[NB], vbx[NB], vby[NB], wb[NB], minv[NB], iinv[NB]; };
 
-// a joint row's pre-stepped terms (constant over the sweep: read from the LDS view) and what the row writes
-struct RegCons {
-    double r1x, r1y, r2x, r2y, k11, k12, k21, k22, bias, bias2, jmax, ratio, ratio_inv, isum, rate, wcoef;
-};
-struct RegAcc { double jacc, jacc2, twrn; };
-
-// compile-time body slot (constraints; b < 0 = the static body)
-template <int NB>
-MG_DEV void rapply(RegBodies<NB> &R, int b, V2 j, V2 r) {
-    if (b < 0) return;
-    R.vx[b] = R.vx[b] + j.x * R.minv[b];
-    R.vy[b] = R.vy[b] + j.y * R.minv[b];
-    R.w[b] += R.iinv[b] * vcross(r, j);
+// compile-time body slot K as a row's side (K < 0: the static body, zeros, nothing put back)
+template <int K, int NB>
+MG_DEV Side rside_get(const RegBodies<NB> &R) {
+    if constexpr (K < 0) return Side{};
+    else return {R.vx[K], R.vy[K], R.w[K], R.vbx[K], R.vby[K], R.wb[K], R.minv[K], R.iinv[K]};
 }
-template <int NB> MG_DEV V2 rv(const RegBodies<NB> &R, int b) { return b < 0 ? v2(0.0, 0.0) : v2(R.vx[b], R.vy[b]); }
-template <int NB> MG_DEV double rw(const RegBodies<NB> &R, int b) { return b < 0 ? 0.0 : R.w[b]; }
-template <int NB> MG_DEV double rii(const RegBodies<NB> &R, int b) { return b < 0 ? 0.0 : R.iinv[b]; }
+template <int K, int NB>
+MG_DEV void rside_put(RegBodies<NB> &R, const Side &x) {
+    if constexpr (K >= 0) {
+        R.vx[K] = x.vx; R.vy[K] = x.vy; R.w[K] = x.w;
+        R.vbx[K] = x.vbx; R.vby[K] = x.vby; R.wb[K] = x.wb;
+    }
+}
 
 template <int NB>
 MG_DEV void rb_load(RegBodies<NB> &R, const MGState &S, int e) {
@@ -387,120 +409,22 @@ MG_DEV void rb_store(const RegBodies<NB> &R, const MGState &S, int e) {
     }
 }
 
-MG_DEV void rc_load(RegCons &q, const MGState &S, int e, int c, int type, double dt) {
-    q = RegCons{};
-    q.jmax = CPA(CP_MAXF, c) * dt;
-    q.isum = CPA(CP_ISUM, c); q.bias = CPA(CP_BIAS, c);
-    if (type == MG_C_PIVOT) {
-        q.bias2 = CPA(CP_BIAS2, c);
-        q.r1x = CPA(CP_R1X, c); q.r1y = CPA(CP_R1Y, c); q.r2x = CPA(CP_R2X, c); q.r2y = CPA(CP_R2Y, c);
-        q.k11 = CPA(CP_K11, c); q.k12 = CPA(CP_K12, c); q.k21 = CPA(CP_K21, c); q.k22 = CPA(CP_K22, c);
-    }
-    if (type == MG_C_GEAR) { q.ratio = CPA(CP_RATIO, c); q.ratio_inv = CPA(CP_RATIO_INV, c); }
-    if (type == MG_C_MOTOR) q.rate = CPA(CP_RATE, c);
-    if (type == MG_C_SPRING) q.wcoef = CPA(CP_WCOEF, c);
+// joint C of the compile-time list (static_cons(C)) on the body registers
+template <int C, int NB>
+MG_DEV void rcons_cached(RegBodies<NB> &R, const RegCons &q, const RegAcc &acc, double dt_coef) {
+    constexpr ConsDesc d = static_cons(C);
+    Side A = rside_get<d.a>(R), B = rside_get<d.b>(R);
+    joint_cached<(d.a >= 0), (d.b >= 0)>(d.type, q, acc, A, B, dt_coef);
+    rside_put<d.a>(R, A);
+    rside_put<d.b>(R, B);
 }
-MG_DEV void ra_load(RegAcc &j, const MGState &S, int e, int c, int type) {
-    j.jacc = CPA(CP_JACC, c); j.jacc2 = 0.0; j.twrn = 0.0;
-    if (type == MG_C_PIVOT) j.jacc2 = CPA(CP_JACC2, c);
-    if (type == MG_C_SPRING) j.twrn = CPA(CP_TWRN, c);
-}
-MG_DEV void ra_store(const RegAcc &j, const MGState &S, int e, int c, int type) {
-    CPA(CP_JACC, c) = j.jacc;
-    if (type == MG_C_PIVOT) CPA(CP_JACC2, c) = j.jacc2;
-    if (type == MG_C_SPRING) CPA(CP_TWRN, c) = j.twrn;
-}
-
-template <int NB>
-MG_DEV void rcons_cached(RegBodies<NB> &R, const RegCons &q, const RegAcc &acc, int a, int b, int type, double dt_coef) {
-    switch (type) {
-    case MG_C_PIVOT: {
-        V2 j = vmult(v2(acc.jacc, acc.jacc2), dt_coef);
-        rapply(R, a, vneg(j), v2(q.r1x, q.r1y));
-        rapply(R, b, j, v2(q.r2x, q.r2y));
-        break;
-    }
-    case MG_C_GEAR: {
-        double j = acc.jacc * dt_coef;
-        if (a >= 0) R.w[a] -= j * R.iinv[a] * q.ratio_inv;
-        if (b >= 0) R.w[b] += j * R.iinv[b];
-        break;
-    }
-    case MG_C_ROTLIMIT:
-    case MG_C_MOTOR: {
-        double j = acc.jacc * dt_coef;
-        if (a >= 0) R.w[a] -= j * R.iinv[a];
-        if (b >= 0) R.w[b] += j * R.iinv[b];
-        break;
-    }
-    default: break;
-    }
-}
-
-template <int NB>
-MG_DEV void rcons_apply(RegBodies<NB> &R, const RegCons &q, RegAcc &acc, int a, int b, int type) {
-    switch (type) {
-    case MG_C_PIVOT: {
-        V2 r1 = v2(q.r1x, q.r1y), r2 = v2(q.r2x, q.r2y);
-        V2 v1 = vadd(rv(R, a), vmult(vperp(r1), rw(R, a)));
-        V2 v2_ = vadd(rv(R, b), vmult(vperp(r2), rw(R, b)));
-        V2 vr = vsub(v2_, v1);
-        V2 d = vsub(v2(q.bias, q.bias2), vr);
-        V2 j = v2(d.x * q.k11 + d.y * q.k12, d.x * q.k21 + d.y * q.k22);
-        V2 jOld = v2(acc.jacc, acc.jacc2);
-        V2 jAcc = vclamp(vadd(jOld, j), q.jmax);
-        acc.jacc = jAcc.x; acc.jacc2 = jAcc.y;
-        V2 dj = vsub(jAcc, jOld);
-        rapply(R, a, vneg(dj), r1);
-        rapply(R, b, dj, r2);
-        break;
-    }
-    case MG_C_GEAR: {
-        double wr = rw(R, b) * q.ratio - rw(R, a);
-        double j = (q.bias - wr) * q.isum;
-        double jOld = acc.jacc;
-        double jAcc = cpclamp(jOld + j, -q.jmax, q.jmax);
-        acc.jacc = jAcc;
-        j = jAcc - jOld;
-        if (a >= 0) R.w[a] -= j * R.iinv[a] * q.ratio_inv;
-        if (b >= 0) R.w[b] += j * R.iinv[b];
-        break;
-    }
-    case MG_C_ROTLIMIT: {
-        double bias = q.bias;
-        if (!bias) return;
-        double wr = rw(R, b) - rw(R, a);
-        double j = -(bias + wr) * q.isum;
-        double jOld = acc.jacc;
-        double jAcc = bias < 0.0 ? cpclamp(jOld + j, 0.0, q.jmax) : cpclamp(jOld + j, -q.jmax, 0.0);
-        acc.jacc = jAcc;
-        j = jAcc - jOld;
-        if (a >= 0) R.w[a] -= j * R.iinv[a];
-        if (b >= 0) R.w[b] += j * R.iinv[b];
-        break;
-    }
-    case MG_C_MOTOR: {
-        double wr = rw(R, b) - rw(R, a) + q.rate;
-        double j = -wr * q.isum;
-        double jOld = acc.jacc;
-        double jAcc = cpclamp(jOld + j, -q.jmax, q.jmax);
-        acc.jacc = jAcc;
-        j = jAcc - jOld;
-        if (a >= 0) R.w[a] -= j * R.iinv[a];
-        if (b >= 0) R.w[b] += j * R.iinv[b];
-        break;
-    }
-    case MG_C_SPRING: {
-        double wrn = rw(R, a) - rw(R, b);
-        double w_damp = (acc.twrn - wrn) * q.wcoef;
-        acc.twrn = wrn + w_damp;
-        double j_damp = w_damp * q.isum;
-        acc.jacc += j_damp;
-        if (a >= 0) R.w[a] += j_damp * R.iinv[a];
-        if (b >= 0) R.w[b] -= j_damp * R.iinv[b];
-        break;
-    }
-    }
+template <int C, int NB>
+MG_DEV void rcons_apply(RegBodies<NB> &R, const RegCons &q, RegAcc &acc) {
+    constexpr ConsDesc d = static_cons(C);
+    Side A = rside_get<d.a>(R), B = rside_get<d.b>(R);
+    joint_row<(d.a >= 0), (d.b >= 0)>(d.type, q, acc, A, B);
+    rside_put<d.a>(R, A);
+    rside_put<d.b>(R, B);
 }
 
 // Arbiter body slots of the compile-time scenes: only the bodies that carry shapes (robot 0, fingers 4-5,
@@ -531,6 +455,9 @@ MG_DEV void hput(double (&x)[NB], const ArbBody<NB> &h, double v) {
     for (int k = 0; k < NB; k++)
         if (shape_body_slot(k)) x[k] = h.m[k] ? v : x[k];
 }
+// The select form keeps its own text of contact_row / contact_cached (mg_rows.h; edit them in step), reading each
+// value through its select chain where it is used: gathered into two Sides first, the same row holds 12 more doubles beside all of
+// RegBodies and step_kernel<6, 16> (at 256 + 254 registers) spills ("Shared solver rows").
 template <int NB>
 MG_DEV void happly(RegBodies<NB> &R, const ArbBody<NB> &h, double minv, double iinv, V2 j, V2 r) {
     hput(R.vx, h, hsel(R.vx, h) + j.x * minv);
@@ -607,81 +534,32 @@ MG_DEV void harb_apply(RegBodies<NB> &R, const MGState &S, int e, int slot) {
 
 // harb_apply with compile-time body slots A / B (< 0: the static body): the arbiter pairs the compile-time
 // scenes produce (robot body / finger / block against a wall or the block) touch body registers by constant
-// index instead of through one-hot selects (harb_apply: ~230 selects per contact).  The same operations in the
-// same order as harb_apply: a static side contributes velocity +0.0 and receives nothing, as there.
+// index instead of through one-hot selects.
 template <int NB, int A, int B>
 MG_DEV void harb_apply_k(RegBodies<NB> &R, const MGState &S, int e, int slot) {
-    const double am = A >= 0 ? R.minv[A] : 0.0, ai = A >= 0 ? R.iinv[A] : 0.0;
-    const double bm = B >= 0 ? R.minv[B] : 0.0, bi = B >= 0 ? R.iinv[B] : 0.0;
+    Side a = rside_get<A>(R), b = rside_get<B>(R);
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     double friction = AT(S.au, slot);
     int cnt = AT(S.acount, slot);
     for (int k = 0; k < cnt; k++) {
-        double nMass = ACON(k, AC_NMASS, slot);
-        V2 r1 = v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)), r2 = v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot));
-        V2 vb1 = v2(0.0, 0.0), v1 = v2(0.0, 0.0), vb2 = v2(0.0, 0.0), v2_ = v2(0.0, 0.0);
-        if constexpr (A >= 0) {
-            vb1 = vadd(v2(R.vbx[A], R.vby[A]), vmult(vperp(r1), R.wb[A]));
-            v1 = vadd(v2(R.vx[A], R.vy[A]), vmult(vperp(r1), R.w[A]));
-        }
-        if constexpr (B >= 0) {
-            vb2 = vadd(v2(R.vbx[B], R.vby[B]), vmult(vperp(r2), R.wb[B]));
-            v2_ = vadd(v2(R.vx[B], R.vy[B]), vmult(vperp(r2), R.w[B]));
-        }
-        V2 vr = vsub(v2_, v1);
-        double vbn = vdot(vsub(vb2, vb1), n);
-        double vrn = vdot(vr, n);
-        double vrt = vdot(vr, vperp(n));
-        double jbn = (ACON(k, AC_BIAS, slot) - vbn) * nMass;
-        double jbnOld = ACON(k, AC_JB, slot);
-        double jBias = cpmax(jbnOld + jbn, 0.0);
-        ACON(k, AC_JB, slot) = jBias;
-        double jn = -(0.0 + vrn) * nMass;
-        double jnOld = ACON(k, AC_JN, slot);
-        double jnAcc = cpmax(jnOld + jn, 0.0);
-        ACON(k, AC_JN, slot) = jnAcc;
-        double jtMax = friction * jnAcc;
-        double jt = -vrt * ACON(k, AC_TMASS, slot);
-        double jtOld = ACON(k, AC_JT, slot);
-        double jtAcc = cpclamp(jtOld + jt, -jtMax, jtMax);
-        ACON(k, AC_JT, slot) = jtAcc;
-        V2 jb = vmult(n, jBias - jbnOld);
-        if constexpr (A >= 0) {
-            const V2 m = vneg(jb);
-            R.vbx[A] = R.vbx[A] + m.x * am; R.vby[A] = R.vby[A] + m.y * am; R.wb[A] = R.wb[A] + ai * vcross(r1, m);
-        }
-        if constexpr (B >= 0) {
-            R.vbx[B] = R.vbx[B] + jb.x * bm; R.vby[B] = R.vby[B] + jb.y * bm; R.wb[B] = R.wb[B] + bi * vcross(r2, jb);
-        }
-        V2 j = vrotate(n, v2(jnAcc - jnOld, jtAcc - jtOld));
-        if constexpr (A >= 0) {
-            const V2 m = vneg(j);
-            R.vx[A] = R.vx[A] + m.x * am; R.vy[A] = R.vy[A] + m.y * am; R.w[A] = R.w[A] + ai * vcross(r1, m);
-        }
-        if constexpr (B >= 0) {
-            R.vx[B] = R.vx[B] + j.x * bm; R.vy[B] = R.vy[B] + j.y * bm; R.w[B] = R.w[B] + bi * vcross(r2, j);
-        }
+        ContactAcc acc = acon_acc(S, e, slot, k);
+        contact_row<(A >= 0), (B >= 0)>(a, b, acon_terms(S, e, slot, k), acc, n, friction);
+        acon_acc_store(S, e, slot, k, acc);
     }
+    rside_put<A>(R, a);
+    rside_put<B>(R, b);
 }
 
 // harb_cached with compile-time body slots (applyCachedImpulse of one arbiter; see harb_apply_k)
 template <int NB, int A, int B>
 MG_DEV void harb_cached_k(RegBodies<NB> &R, const MGState &S, int e, int slot, double dt_coef) {
-    const double am = A >= 0 ? R.minv[A] : 0.0, ai = A >= 0 ? R.iinv[A] : 0.0;
-    const double bm = B >= 0 ? R.minv[B] : 0.0, bi = B >= 0 ? R.iinv[B] : 0.0;
+    Side a = rside_get<A>(R), b = rside_get<B>(R);
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     int cnt = AT(S.acount, slot);
-    for (int k = 0; k < cnt; k++) {
-        V2 j = vmult(vrotate(n, v2(ACON(k, AC_JN, slot), ACON(k, AC_JT, slot))), dt_coef);
-        if constexpr (A >= 0) {
-            const V2 m = vneg(j), r1 = v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot));
-            R.vx[A] = R.vx[A] + m.x * am; R.vy[A] = R.vy[A] + m.y * am; R.w[A] = R.w[A] + ai * vcross(r1, m);
-        }
-        if constexpr (B >= 0) {
-            const V2 r2 = v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot));
-            R.vx[B] = R.vx[B] + j.x * bm; R.vy[B] = R.vy[B] + j.y * bm; R.w[B] = R.w[B] + bi * vcross(r2, j);
-        }
-    }
+    for (int k = 0; k < cnt; k++)
+        contact_cached<(A >= 0), (B >= 0)>(a, b, acon_terms(S, e, slot, k), acon_acc(S, e, slot, k), n, dt_coef);
+    rside_put<A>(R, a);
+    rside_put<B>(R, b);
 }
 
 // applyCachedImpulse of one arbiter of the compile-time scenes, dispatched as harb_row
@@ -722,11 +600,12 @@ MG_DEV void harb_row(RegBodies<NB> &R, const MGState &S, int e, int slot) {
 // The first NARB active arbiters of a substep in registers for the 10 iterations (the compile-time scenes
 // rarely hold more: MoveToRegion has live arbiters in 3.5% of env-substeps, MoveToCorner 10%): their pair code,
 // normal, friction and contacts' pre-stepped terms are read from LDS once per substep instead of once per
-// iteration, the accumulated impulses stay in registers and are written back after the sweep.  Same operations
-// in the same order as harb_apply.
+// iteration, the accumulated impulses stay in registers and are written back after the sweep.
 struct RegArb {
     int code, cnt;
-    double nx, ny, fr, nm[2], r1x[2], r1y[2], r2x[2], r2y[2], bias[2], tm[2], jb[2], jn[2], jt[2];
+    double nx, ny, fr;
+    ContactTerms t[2];
+    ContactAcc acc[2];
 };
 // pair code of an arbiter's (body A, body B) in the compile-time scenes (harb_row's cases), -1: other
 MG_DEV int arb_pair_code(int sa, int sb) {
@@ -744,71 +623,24 @@ MG_DEV void rarb_load(RegArb &a, const MGState &S, int e, int slot) {
     a.cnt = AT(S.acount, slot);
     a.nx = AT(S.anx, slot); a.ny = AT(S.any, slot); a.fr = AT(S.au, slot);
 #pragma unroll
-    for (int k = 0; k < 2; k++) {
-        a.nm[k] = ACON(k, AC_NMASS, slot); a.bias[k] = ACON(k, AC_BIAS, slot); a.tm[k] = ACON(k, AC_TMASS, slot);
-        a.r1x[k] = ACON(k, AC_R1X, slot); a.r1y[k] = ACON(k, AC_R1Y, slot);
-        a.r2x[k] = ACON(k, AC_R2X, slot); a.r2y[k] = ACON(k, AC_R2Y, slot);
-        a.jb[k] = ACON(k, AC_JB, slot); a.jn[k] = ACON(k, AC_JN, slot); a.jt[k] = ACON(k, AC_JT, slot);
-    }
+    for (int k = 0; k < 2; k++) { a.t[k] = acon_terms(S, e, slot, k); a.acc[k] = acon_acc(S, e, slot, k); }
 }
 MG_DEV void rarb_store(const RegArb &a, const MGState &S, int e, int slot) {
 #pragma unroll
     for (int k = 0; k < 2; k++)
-        if (k < a.cnt) { ACON(k, AC_JB, slot) = a.jb[k]; ACON(k, AC_JN, slot) = a.jn[k]; ACON(k, AC_JT, slot) = a.jt[k]; }
+        if (k < a.cnt) acon_acc_store(S, e, slot, k, a.acc[k]);
 }
 template <int NB, int A, int B>
-MG_DEV void rarb_apply_k(RegBodies<NB> &R, RegArb &a) {
-    const double am = A >= 0 ? R.minv[A] : 0.0, ai = A >= 0 ? R.iinv[A] : 0.0;
-    const double bm = B >= 0 ? R.minv[B] : 0.0, bi = B >= 0 ? R.iinv[B] : 0.0;
-    const V2 n = v2(a.nx, a.ny);
+MG_DEV void rarb_apply_k(RegBodies<NB> &R, RegArb &r) {
+    Side a = rside_get<A>(R), b = rside_get<B>(R);
+    const V2 n = v2(r.nx, r.ny);
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-        if (k >= a.cnt) break;
-        const double nMass = a.nm[k];
-        V2 r1 = v2(a.r1x[k], a.r1y[k]), r2 = v2(a.r2x[k], a.r2y[k]);
-        V2 vb1 = v2(0.0, 0.0), v1 = v2(0.0, 0.0), vb2 = v2(0.0, 0.0), v2_ = v2(0.0, 0.0);
-        if constexpr (A >= 0) {
-            vb1 = vadd(v2(R.vbx[A], R.vby[A]), vmult(vperp(r1), R.wb[A]));
-            v1 = vadd(v2(R.vx[A], R.vy[A]), vmult(vperp(r1), R.w[A]));
-        }
-        if constexpr (B >= 0) {
-            vb2 = vadd(v2(R.vbx[B], R.vby[B]), vmult(vperp(r2), R.wb[B]));
-            v2_ = vadd(v2(R.vx[B], R.vy[B]), vmult(vperp(r2), R.w[B]));
-        }
-        V2 vr = vsub(v2_, v1);
-        double vbn = vdot(vsub(vb2, vb1), n);
-        double vrn = vdot(vr, n);
-        double vrt = vdot(vr, vperp(n));
-        double jbn = (a.bias[k] - vbn) * nMass;
-        double jbnOld = a.jb[k];
-        double jBias = cpmax(jbnOld + jbn, 0.0);
-        a.jb[k] = jBias;
-        double jn = -(0.0 + vrn) * nMass;
-        double jnOld = a.jn[k];
-        double jnAcc = cpmax(jnOld + jn, 0.0);
-        a.jn[k] = jnAcc;
-        double jtMax = a.fr * jnAcc;
-        double jt = -vrt * a.tm[k];
-        double jtOld = a.jt[k];
-        double jtAcc = cpclamp(jtOld + jt, -jtMax, jtMax);
-        a.jt[k] = jtAcc;
-        V2 jb = vmult(n, jBias - jbnOld);
-        if constexpr (A >= 0) {
-            const V2 m = vneg(jb);
-            R.vbx[A] = R.vbx[A] + m.x * am; R.vby[A] = R.vby[A] + m.y * am; R.wb[A] = R.wb[A] + ai * vcross(r1, m);
-        }
-        if constexpr (B >= 0) {
-            R.vbx[B] = R.vbx[B] + jb.x * bm; R.vby[B] = R.vby[B] + jb.y * bm; R.wb[B] = R.wb[B] + bi * vcross(r2, jb);
-        }
-        V2 j = vrotate(n, v2(jnAcc - jnOld, jtAcc - jtOld));
-        if constexpr (A >= 0) {
-            const V2 m = vneg(j);
-            R.vx[A] = R.vx[A] + m.x * am; R.vy[A] = R.vy[A] + m.y * am; R.w[A] = R.w[A] + ai * vcross(r1, m);
-        }
-        if constexpr (B >= 0) {
-            R.vx[B] = R.vx[B] + j.x * bm; R.vy[B] = R.vy[B] + j.y * bm; R.w[B] = R.w[B] + bi * vcross(r2, j);
-        }
+        if (k >= r.cnt) break;
+        contact_row<(A >= 0), (B >= 0)>(a, b, r.t[k], r.acc[k], n, r.fr);
     }
+    rside_put<A>(R, a);
+    rside_put<B>(R, b);
 }
 // a register arbiter's row (its code is one of arb_pair_code's: rarb_ok checked it at load)
 template <int NB>
@@ -854,16 +686,14 @@ MG_DEV void rstatic_store(const RegAcc *acc, const MGState &S, int e) {
 template <int NCS, int NB, int C = 0>
 MG_DEV void rstatic_cached(RegBodies<NB> &R, const RegCons *q, const RegAcc *acc, double dt_coef) {
     if constexpr (C < NCS) {
-        constexpr ConsDesc d = static_cons(C);
-        rcons_cached(R, q[C], acc[C], d.a, d.b, d.type, dt_coef);
+        rcons_cached<C>(R, q[C], acc[C], dt_coef);
         rstatic_cached<NCS, NB, C + 1>(R, q, acc, dt_coef);
     }
 }
 template <int NCS, int NB, int C = 0>
 MG_DEV void rstatic_apply(RegBodies<NB> &R, const RegCons *q, RegAcc *acc) {
     if constexpr (C < NCS) {
-        constexpr ConsDesc d = static_cons(C);
-        rcons_apply(R, q[C], acc[C], d.a, d.b, d.type);
+        rcons_apply<C>(R, q[C], acc[C]);
         rstatic_apply<NCS, NB, C + 1>(R, q, acc);
     }
 }
@@ -877,11 +707,10 @@ template <int NCS, int NB, int C = 0>
 MG_DEV void rstream_cached(RegBodies<NB> &R, RegCons &cur, const RegAcc *acc, const MGState &S, int e, double dt,
                            double dt_coef) {
     if constexpr (C < NCS) {
-        constexpr ConsDesc d = static_cons(C);
         constexpr int N = (C + 1) % NCS;
         RegCons nxt;
         rc_load(nxt, S, e, N, static_cons(N).type, dt);
-        rcons_cached(R, cur, acc[C], d.a, d.b, d.type, dt_coef);
+        rcons_cached<C>(R, cur, acc[C], dt_coef);
         cur = nxt;
         rstream_cached<NCS, NB, C + 1>(R, cur, acc, S, e, dt, dt_coef);
     }
@@ -890,18 +719,17 @@ MG_DEV void rstream_cached(RegBodies<NB> &R, RegCons &cur, const RegAcc *acc, co
 template <int NCS, int NB, bool ACCW, int C = 0>
 MG_DEV void rstream_apply(RegBodies<NB> &R, RegCons &cur, RegAcc *acc, const MGState &S, int e, double dt) {
     if constexpr (C < NCS) {
-        constexpr ConsDesc d = static_cons(C);
         constexpr int N = (C + 1) % NCS;
         RegCons nxt;
         RegAcc nacc;
         rc_load(nxt, S, e, N, static_cons(N).type, dt);
         if constexpr (ACCW) {
             ra_load(nacc, S, e, N, static_cons(N).type);
-            rcons_apply(R, cur, acc[0], d.a, d.b, d.type);
-            ra_store(acc[0], S, e, C, d.type);
+            rcons_apply<C>(R, cur, acc[0]);
+            ra_store(acc[0], S, e, C, static_cons(C).type);
             acc[0] = nacc;
         } else {
-            rcons_apply(R, cur, acc[C], d.a, d.b, d.type);
+            rcons_apply<C>(R, cur, acc[C]);
         }
         cur = nxt;
         rstream_apply<NCS, NB, ACCW, C + 1>(R, cur, acc, S, e, dt);
@@ -1070,175 +898,79 @@ MG_DEV uint64_t rl_u64(uint64_t v, int src) {
 MG_DEV int pair_row_off(int i, int ns) { return i * (ns + 3) - (i * (i - 1)) / 2; }
 
 // The serial sweep of the cooperative step keeps the body velocities in the wavefront's VGPRs, spread
-// over the lanes (lane b holds body b): every lane runs the sweep on the same (uniform) values, reading
+// over the lanes (lane b holds body b's side): every lane runs the sweep on the same (uniform) values, reading
 // a body with readlane by its wave-uniform slot and writing it with a lane-select, so no body state
-// makes an LDS round trip.  Same operations in the same order as cons_*_impl / arbiter_*.
-struct LaneBodies { double vx, vy, w, vbx, vby, wb, minv, iinv; };
+// makes an LDS round trip.
+using LaneBodies = Side;
 MG_DEV int ufirst(int v) { return __builtin_amdgcn_readfirstlane(v); }
 MG_DEV double lget(double f, int b) { return b < 0 ? 0.0 : rl_d(f, b); }
 MG_DEV void lput(double &f, int b, int lane, double v) { f = lane == b ? v : f; }
-MG_DEV void lapply(LaneBodies &R, int lane, int b, V2 j, V2 r) {
+MG_DEV Side lside_get(const LaneBodies &R, int b) {   // the static body (b < 0): zeros
+    return {lget(R.vx, b), lget(R.vy, b), lget(R.w, b), lget(R.vbx, b), lget(R.vby, b), lget(R.wb, b),
+            lget(R.minv, b), lget(R.iinv, b)};
+}
+// lin: the row changes the linear velocity too (a pivot, a contact)
+MG_DEV void lside_put(LaneBodies &R, int b, int lane, const Side &x, bool lin) {
     if (b < 0) return;
-    const double minv = lget(R.minv, b), iinv = lget(R.iinv, b);
-    lput(R.vx, b, lane, lget(R.vx, b) + j.x * minv);
-    lput(R.vy, b, lane, lget(R.vy, b) + j.y * minv);
-    lput(R.w, b, lane, lget(R.w, b) + iinv * vcross(r, j));
+    if (lin) { lput(R.vx, b, lane, x.vx); lput(R.vy, b, lane, x.vy); }
+    lput(R.w, b, lane, x.w);
 }
-MG_DEV void lapply_bias(LaneBodies &R, int lane, int b, V2 j, V2 r) {
+MG_DEV void lside_put_bias(LaneBodies &R, int b, int lane, const Side &x) {
     if (b < 0) return;
-    const double minv = lget(R.minv, b), iinv = lget(R.iinv, b);
-    lput(R.vbx, b, lane, lget(R.vbx, b) + j.x * minv);
-    lput(R.vby, b, lane, lget(R.vby, b) + j.y * minv);
-    lput(R.wb, b, lane, lget(R.wb, b) + iinv * vcross(r, j));
-}
-MG_DEV void ladd_w(LaneBodies &R, int lane, int b, double dw) { // AT(S.bw, b) += dw
-    if (b >= 0) lput(R.w, b, lane, lget(R.w, b) + dw);
-}
-MG_DEV void lsub_w(LaneBodies &R, int lane, int b, double dw) { // AT(S.bw, b) -= dw
-    if (b >= 0) lput(R.w, b, lane, lget(R.w, b) - dw);
+    lput(R.vbx, b, lane, x.vbx); lput(R.vby, b, lane, x.vby); lput(R.wb, b, lane, x.wb);
 }
 
 MG_DEV void lcons_cached(LaneBodies &R, int lane, const MGState &S, int e, int c, int a, int b, int type,
                          double dt_coef) {
-    switch (type) {
-    case MG_C_PIVOT: {
-        V2 j = vmult(v2(CPA(CP_JACC, c), CPA(CP_JACC2, c)), dt_coef);
-        lapply(R, lane, a, vneg(j), v2(CPA(CP_R1X, c), CPA(CP_R1Y, c)));
-        lapply(R, lane, b, j, v2(CPA(CP_R2X, c), CPA(CP_R2Y, c)));
-        break;
-    }
-    case MG_C_GEAR: {
-        double j = CPA(CP_JACC, c) * dt_coef;
-        lsub_w(R, lane, a, j * lget(R.iinv, a) * CPA(CP_RATIO_INV, c));
-        ladd_w(R, lane, b, j * lget(R.iinv, b));
-        break;
-    }
-    case MG_C_ROTLIMIT:
-    case MG_C_MOTOR: {
-        double j = CPA(CP_JACC, c) * dt_coef;
-        lsub_w(R, lane, a, j * lget(R.iinv, a));
-        ladd_w(R, lane, b, j * lget(R.iinv, b));
-        break;
-    }
-    default: break;
-    }
+    RegCons q;
+    RegAcc acc;
+    rc_load(q, S, e, c, type, 0.0);   // a warm start reads no jmax
+    ra_load(acc, S, e, c, type);
+    Side A = lside_get(R, a), B = lside_get(R, b);
+    joint_cached<true, true>(type, q, acc, A, B, dt_coef);
+    lside_put(R, a, lane, A, type == MG_C_PIVOT);
+    lside_put(R, b, lane, B, type == MG_C_PIVOT);
 }
 
 MG_DEV void lcons_apply(LaneBodies &R, int lane, const MGState &S, int e, int c, int a, int b, int type, double dt) {
-    switch (type) {
-    case MG_C_PIVOT: {
-        V2 r1 = v2(CPA(CP_R1X, c), CPA(CP_R1Y, c)), r2 = v2(CPA(CP_R2X, c), CPA(CP_R2Y, c));
-        V2 v1 = vadd(v2(lget(R.vx, a), lget(R.vy, a)), vmult(vperp(r1), lget(R.w, a)));
-        V2 v2_ = vadd(v2(lget(R.vx, b), lget(R.vy, b)), vmult(vperp(r2), lget(R.w, b)));
-        V2 vr = vsub(v2_, v1);
-        V2 d = vsub(v2(CPA(CP_BIAS, c), CPA(CP_BIAS2, c)), vr);
-        V2 j = v2(d.x * CPA(CP_K11, c) + d.y * CPA(CP_K12, c), d.x * CPA(CP_K21, c) + d.y * CPA(CP_K22, c));
-        V2 jOld = v2(CPA(CP_JACC, c), CPA(CP_JACC2, c));
-        V2 jAcc = vclamp(vadd(jOld, j), CPA(CP_MAXF, c) * dt);
-        if (lane == 0) { CPA(CP_JACC, c) = jAcc.x; CPA(CP_JACC2, c) = jAcc.y; }
-        V2 dj = vsub(jAcc, jOld);
-        lapply(R, lane, a, vneg(dj), r1);
-        lapply(R, lane, b, dj, r2);
-        break;
-    }
-    case MG_C_GEAR: {
-        double ratio = CPA(CP_RATIO, c);
-        double wr = lget(R.w, b) * ratio - lget(R.w, a);
-        double jMax = CPA(CP_MAXF, c) * dt;
-        double j = (CPA(CP_BIAS, c) - wr) * CPA(CP_ISUM, c);
-        double jOld = CPA(CP_JACC, c);
-        double jAcc = cpclamp(jOld + j, -jMax, jMax);
-        if (lane == 0) CPA(CP_JACC, c) = jAcc;
-        j = jAcc - jOld;
-        lsub_w(R, lane, a, j * lget(R.iinv, a) * CPA(CP_RATIO_INV, c));
-        ladd_w(R, lane, b, j * lget(R.iinv, b));
-        break;
-    }
-    case MG_C_ROTLIMIT: {
-        double bias = CPA(CP_BIAS, c);
-        if (!bias) return;
-        double wr = lget(R.w, b) - lget(R.w, a);
-        double jMax = CPA(CP_MAXF, c) * dt;
-        double j = -(bias + wr) * CPA(CP_ISUM, c);
-        double jOld = CPA(CP_JACC, c);
-        double jAcc = bias < 0.0 ? cpclamp(jOld + j, 0.0, jMax) : cpclamp(jOld + j, -jMax, 0.0);
-        if (lane == 0) CPA(CP_JACC, c) = jAcc;
-        j = jAcc - jOld;
-        lsub_w(R, lane, a, j * lget(R.iinv, a));
-        ladd_w(R, lane, b, j * lget(R.iinv, b));
-        break;
-    }
-    case MG_C_MOTOR: {
-        double wr = lget(R.w, b) - lget(R.w, a) + CPA(CP_RATE, c);
-        double jMax = CPA(CP_MAXF, c) * dt;
-        double j = -wr * CPA(CP_ISUM, c);
-        double jOld = CPA(CP_JACC, c);
-        double jAcc = cpclamp(jOld + j, -jMax, jMax);
-        if (lane == 0) CPA(CP_JACC, c) = jAcc;
-        j = jAcc - jOld;
-        lsub_w(R, lane, a, j * lget(R.iinv, a));
-        ladd_w(R, lane, b, j * lget(R.iinv, b));
-        break;
-    }
-    case MG_C_SPRING: {
-        double wrn = lget(R.w, a) - lget(R.w, b);
-        double w_damp = (CPA(CP_TWRN, c) - wrn) * CPA(CP_WCOEF, c);
-        double j_damp = w_damp * CPA(CP_ISUM, c);
-        double jacc = CPA(CP_JACC, c) + j_damp;
-        if (lane == 0) { CPA(CP_TWRN, c) = wrn + w_damp; CPA(CP_JACC, c) = jacc; }
-        ladd_w(R, lane, a, j_damp * lget(R.iinv, a));
-        lsub_w(R, lane, b, j_damp * lget(R.iinv, b));
-        break;
-    }
-    }
+    RegCons q;
+    RegAcc acc;
+    rc_load(q, S, e, c, type, dt);
+    ra_load(acc, S, e, c, type);
+    Side A = lside_get(R, a), B = lside_get(R, b);
+    joint_row<true, true>(type, q, acc, A, B);
+    if (lane == 0) ra_store(acc, S, e, c, type);
+    lside_put(R, a, lane, A, type == MG_C_PIVOT);
+    lside_put(R, b, lane, B, type == MG_C_PIVOT);
 }
 
 MG_DEV void larb_cached(LaneBodies &R, int lane, const MGState &S, int e, int slot, double dt_coef) {
     if (ufirst(AT(S.astate, slot)) == ARB_FIRST) return;
     const int a = ufirst(AT(S.asa, slot)), b = ufirst(AT(S.asb, slot));
+    Side A = lside_get(R, a), B = lside_get(R, b);
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     const int cnt = ufirst(AT(S.acount, slot));
-    for (int k = 0; k < cnt; k++) {
-        V2 j = vmult(vrotate(n, v2(ACON(k, AC_JN, slot), ACON(k, AC_JT, slot))), dt_coef);
-        lapply(R, lane, a, vneg(j), v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)));
-        lapply(R, lane, b, j, v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot)));
-    }
+    for (int k = 0; k < cnt; k++)
+        contact_cached<true, true>(A, B, acon_terms(S, e, slot, k), acon_acc(S, e, slot, k), n, dt_coef);
+    lside_put(R, a, lane, A, true);
+    lside_put(R, b, lane, B, true);
 }
 
 MG_DEV void larb_apply(LaneBodies &R, int lane, const MGState &S, int e, int slot) {
     const int a = ufirst(AT(S.asa, slot)), b = ufirst(AT(S.asb, slot));
+    Side A = lside_get(R, a), B = lside_get(R, b);
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     double friction = AT(S.au, slot);
     const int cnt = ufirst(AT(S.acount, slot));
     for (int k = 0; k < cnt; k++) {
-        double nMass = ACON(k, AC_NMASS, slot);
-        V2 r1 = v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)), r2 = v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot));
-        V2 vb1 = vadd(v2(lget(R.vbx, a), lget(R.vby, a)), vmult(vperp(r1), lget(R.wb, a)));
-        V2 vb2 = vadd(v2(lget(R.vbx, b), lget(R.vby, b)), vmult(vperp(r2), lget(R.wb, b)));
-        V2 v1 = vadd(v2(lget(R.vx, a), lget(R.vy, a)), vmult(vperp(r1), lget(R.w, a)));
-        V2 v2_ = vadd(v2(lget(R.vx, b), lget(R.vy, b)), vmult(vperp(r2), lget(R.w, b)));
-        V2 vr = vsub(v2_, v1);
-        double vbn = vdot(vsub(vb2, vb1), n);
-        double vrn = vdot(vr, n);
-        double vrt = vdot(vr, vperp(n));
-        double jbn = (ACON(k, AC_BIAS, slot) - vbn) * nMass;
-        double jbnOld = ACON(k, AC_JB, slot);
-        double jBias = cpmax(jbnOld + jbn, 0.0);
-        double jn = -(0.0 + vrn) * nMass;
-        double jnOld = ACON(k, AC_JN, slot);
-        double jnAcc = cpmax(jnOld + jn, 0.0);
-        double jtMax = friction * jnAcc;
-        double jt = -vrt * ACON(k, AC_TMASS, slot);
-        double jtOld = ACON(k, AC_JT, slot);
-        double jtAcc = cpclamp(jtOld + jt, -jtMax, jtMax);
-        if (lane == 0) { ACON(k, AC_JB, slot) = jBias; ACON(k, AC_JN, slot) = jnAcc; ACON(k, AC_JT, slot) = jtAcc; }
-        V2 jb = vmult(n, jBias - jbnOld);
-        lapply_bias(R, lane, a, vneg(jb), r1);
-        lapply_bias(R, lane, b, jb, r2);
-        V2 j = vrotate(n, v2(jnAcc - jnOld, jtAcc - jtOld));
-        lapply(R, lane, a, vneg(j), r1);
-        lapply(R, lane, b, j, r2);
+        ContactAcc acc = acon_acc(S, e, slot, k);
+        contact_row<true, true>(A, B, acon_terms(S, e, slot, k), acc, n, friction);
+        if (lane == 0) acon_acc_store(S, e, slot, k, acc);
     }
+    lside_put(R, a, lane, A, true);
+    lside_put(R, b, lane, B, true);
+    lside_put_bias(R, a, lane, A);
+    lside_put_bias(R, b, lane, B);
 }
 
 // A block's ground joints (Pivot + Gear to the static body, entities.py:580-754) touch only the
@@ -1268,7 +1000,9 @@ MG_DEV GroundRows ground_rows(const MGState &S, int e, int lane, int nb, int nc)
 }
 MG_DEV bool is_ground_row(const GroundRows &G, int b) { return b >= 0 && ((G.mask >> b) & 1ull); }
 
-// lcons_cached / lcons_apply of a ground row on the lane that holds body b (body a static)
+// a ground row on the lane that holds its body b (body a static).  The ground rows keep their own text of
+// joint_row / joint_cached (mg_rows.h; edit them in step): on joint_row<false, true> the cooperative form ran 1.3%
+// slower on MatchRegions ("Shared solver rows")
 MG_DEV void lground_cached(LaneBodies &R, const MGState &S, int e, int c, double dt_coef) {
     if (AT(S.ctype, c) == MG_C_PIVOT) {
         V2 j = vmult(v2(CPA(CP_JACC, c), CPA(CP_JACC2, c)), dt_coef);
@@ -1313,13 +1047,12 @@ MG_DEV void lground_apply(LaneBodies &R, const MGState &S, int e, int c, double 
 // bodies (rb0 .. rb0 + 5) and its ten joints' terms live in every lane's registers as in static_solve, so
 // the robot rows (3/4 of the sweep's time when read through readlane / lane-select) index bodies by
 // constants; block bodies stay in their lanes; arbiter rows reach a robot body through a uniform select.
-// Same operations in the same order as lcons_* / larb_*.
 MG_DEV bool is_rob(int b, int rb0) { return b >= rb0 && b < rb0 + 6; }
 // the robot's velocities, masses and joint accumulators (wave-uniform); the bias velocities (touched by
 // arbiter rows only) stay in the bodies' lanes.  Every access to RobotV uses a compile-time slot: a runtime
 // index (even through a select chain, which the compiler folds back into one) puts the whole struct in
 // per-lane scratch memory -- measured in round 3 as ~4 GB of scratch writes per launch at 8192 envs.
-struct RobotV { double vx[6], vy[6], w[6], minv[6], iinv[6], jacc[10], jacc2[10], twrn[10]; };
+struct RobotV { double vx[6], vy[6], w[6], minv[6], iinv[6]; RegAcc acc[10]; };
 // body side of an arbiter row: K >= 0 the robot's body slot K (in RobotV), K < 0 a block body (in its lane) or
 // the static body (b < 0)
 template <int K> MG_DEV double xget(double lf, const double (&rf)[6], int b) {
@@ -1330,96 +1063,49 @@ template <int K> MG_DEV void xput(double &lf, double (&rf)[6], int b, int lane, 
     if constexpr (K >= 0) rf[K] = v;
     else if (b >= 0) lput(lf, b, lane, v);
 }
-template <int K>
-MG_DEV void xapply(LaneBodies &R, RobotV &V, int lane, int b, V2 j, V2 r) {
-    if (K < 0 && b < 0) return;
-    const double minv = xget<K>(R.minv, V.minv, b), iinv = xget<K>(R.iinv, V.iinv, b);
-    xput<K>(R.vx, V.vx, b, lane, xget<K>(R.vx, V.vx, b) + j.x * minv);
-    xput<K>(R.vy, V.vy, b, lane, xget<K>(R.vy, V.vy, b) + j.y * minv);
-    xput<K>(R.w, V.w, b, lane, xget<K>(R.w, V.w, b) + iinv * vcross(r, j));
-}
-template <int K>
-MG_DEV void xapply_bias(LaneBodies &R, RobotV &V, int lane, int b, V2 j, V2 r) {
-    if (b < 0) return;
-    const double minv = xget<K>(R.minv, V.minv, b), iinv = xget<K>(R.iinv, V.iinv, b);
-    lput(R.vbx, b, lane, lget(R.vbx, b) + j.x * minv);
-    lput(R.vby, b, lane, lget(R.vby, b) + j.y * minv);
-    lput(R.wb, b, lane, lget(R.wb, b) + iinv * vcross(r, j));
-}
-template <int KA, int KB>
-MG_DEV void xarb_cached_k(LaneBodies &R, RobotV &V, int lane, const MGState &S, int e, int slot, int a, int b,
-                          int cnt, double dt_coef) {
-    V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
-    for (int k = 0; k < cnt; k++) {
-        V2 j = vmult(vrotate(n, v2(ACON(k, AC_JN, slot), ACON(k, AC_JT, slot))), dt_coef);
-        xapply<KA>(R, V, lane, a, vneg(j), v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)));
-        xapply<KB>(R, V, lane, b, j, v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot)));
-    }
-}
 // one side of an arbiter row, gathered once per row (not per contact) into wave-uniform registers: velocities and
 // masses of a robot body (RobotV slot K >= 0) or of a block body (readlane from its lane), zeros for the static
 // body (b < 0, never written back); bias velocities always live in the body's lane
-struct XSide { double vx, vy, w, vbx, vby, wb, minv, iinv; };
 template <int K>
-MG_DEV XSide xside_get(const LaneBodies &R, const RobotV &V, int b) {
-    XSide x;
+MG_DEV Side xside_get(const LaneBodies &R, const RobotV &V, int b) {
+    Side x;
     x.vx = xget<K>(R.vx, V.vx, b); x.vy = xget<K>(R.vy, V.vy, b); x.w = xget<K>(R.w, V.w, b);
     x.minv = xget<K>(R.minv, V.minv, b); x.iinv = xget<K>(R.iinv, V.iinv, b);
     x.vbx = lget(R.vbx, b); x.vby = lget(R.vby, b); x.wb = lget(R.wb, b);
     return x;
 }
 template <int K>
-MG_DEV void xside_put(LaneBodies &R, RobotV &V, int b, int lane, const XSide &x) {
+MG_DEV void xside_put(LaneBodies &R, RobotV &V, int b, int lane, const Side &x) {
     if (K < 0 && b < 0) return;
     xput<K>(R.vx, V.vx, b, lane, x.vx); xput<K>(R.vy, V.vy, b, lane, x.vy); xput<K>(R.w, V.w, b, lane, x.w);
-    lput(R.vbx, b, lane, x.vbx); lput(R.vby, b, lane, x.vby); lput(R.wb, b, lane, x.wb);
+}
+// a and b are distinct bodies (or the static body), so each side's values are carried across the row's contacts
+// in registers
+template <int KA, int KB>
+MG_DEV void xarb_cached_k(LaneBodies &R, RobotV &V, int lane, const MGState &S, int e, int slot, int a, int b,
+                          int cnt, double dt_coef) {
+    V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
+    Side A = xside_get<KA>(R, V, a), B = xside_get<KB>(R, V, b);
+    for (int k = 0; k < cnt; k++)
+        contact_cached<true, true>(A, B, acon_terms(S, e, slot, k), acon_acc(S, e, slot, k), n, dt_coef);
+    xside_put<KA>(R, V, a, lane, A);
+    xside_put<KB>(R, V, b, lane, B);
 }
 template <int KA, int KB>
 MG_DEV void xarb_apply_k(LaneBodies &R, RobotV &V, int lane, const MGState &S, int e, int slot, int a, int b,
                          int cnt) {
     V2 n = v2(AT(S.anx, slot), AT(S.any, slot));
     double friction = AT(S.au, slot);
-    // a and b are distinct bodies (or the static body), so each side's values can be carried across the row's
-    // contacts in registers: the same reads and writes as per-contact lget / lput, in the same order
-    XSide A = xside_get<KA>(R, V, a), B = xside_get<KB>(R, V, b);
-    const bool da = KA >= 0 || a >= 0, db = KB >= 0 || b >= 0;   // sides that receive impulses
+    Side A = xside_get<KA>(R, V, a), B = xside_get<KB>(R, V, b);
     for (int k = 0; k < cnt; k++) {
-        double nMass = ACON(k, AC_NMASS, slot);
-        V2 r1 = v2(ACON(k, AC_R1X, slot), ACON(k, AC_R1Y, slot)), r2 = v2(ACON(k, AC_R2X, slot), ACON(k, AC_R2Y, slot));
-        V2 vb1 = vadd(v2(A.vbx, A.vby), vmult(vperp(r1), A.wb));
-        V2 vb2 = vadd(v2(B.vbx, B.vby), vmult(vperp(r2), B.wb));
-        V2 v1 = vadd(v2(A.vx, A.vy), vmult(vperp(r1), A.w));
-        V2 v2_ = vadd(v2(B.vx, B.vy), vmult(vperp(r2), B.w));
-        V2 vr = vsub(v2_, v1);
-        double vbn = vdot(vsub(vb2, vb1), n);
-        double vrn = vdot(vr, n);
-        double vrt = vdot(vr, vperp(n));
-        double jbn = (ACON(k, AC_BIAS, slot) - vbn) * nMass;
-        double jbnOld = ACON(k, AC_JB, slot);
-        double jBias = cpmax(jbnOld + jbn, 0.0);
-        double jn = -(0.0 + vrn) * nMass;
-        double jnOld = ACON(k, AC_JN, slot);
-        double jnAcc = cpmax(jnOld + jn, 0.0);
-        double jtMax = friction * jnAcc;
-        double jt = -vrt * ACON(k, AC_TMASS, slot);
-        double jtOld = ACON(k, AC_JT, slot);
-        double jtAcc = cpclamp(jtOld + jt, -jtMax, jtMax);
-        if (lane == 0) { ACON(k, AC_JB, slot) = jBias; ACON(k, AC_JN, slot) = jnAcc; ACON(k, AC_JT, slot) = jtAcc; }
-        V2 jb = vmult(n, jBias - jbnOld);
-        if (a >= 0) {   // xapply_bias: bias velocities of a non-static side
-            const V2 m = vneg(jb);
-            A.vbx = A.vbx + m.x * A.minv; A.vby = A.vby + m.y * A.minv; A.wb = A.wb + A.iinv * vcross(r1, m);
-        }
-        if (b >= 0) { B.vbx = B.vbx + jb.x * B.minv; B.vby = B.vby + jb.y * B.minv; B.wb = B.wb + B.iinv * vcross(r2, jb); }
-        V2 j = vrotate(n, v2(jnAcc - jnOld, jtAcc - jtOld));
-        if (da) {
-            const V2 m = vneg(j);
-            A.vx = A.vx + m.x * A.minv; A.vy = A.vy + m.y * A.minv; A.w = A.w + A.iinv * vcross(r1, m);
-        }
-        if (db) { B.vx = B.vx + j.x * B.minv; B.vy = B.vy + j.y * B.minv; B.w = B.w + B.iinv * vcross(r2, j); }
+        ContactAcc acc = acon_acc(S, e, slot, k);
+        contact_row<true, true>(A, B, acon_terms(S, e, slot, k), acc, n, friction);
+        if (lane == 0) acon_acc_store(S, e, slot, k, acc);
     }
     xside_put<KA>(R, V, a, lane, A);
     xside_put<KB>(R, V, b, lane, B);
+    lside_put_bias(R, a, lane, A);
+    lside_put_bias(R, b, lane, B);
 }
 // Arbiter rows dispatched on their bodies' robot slots (uniform branches, so every RobotV access has a constant
 // slot): only the bodies that carry shapes can be in contact -- the robot body (slot 0) and the fingers (4, 5)
@@ -1451,92 +1137,35 @@ MG_DEV void xarb_row(LaneBodies &R, RobotV &V, int rb0, int lane, const MGState 
     else if (lane == 0) S.overflow[e] |= 32;
 #undef XROW
 }
-// robot joint K (static_cons(K): compile-time type and body slots) at list index c: lcons_cached /
-// lcons_apply with the bodies and accumulators in registers and the pre-stepped terms read from LDS
+// robot joint K (static_cons(K): compile-time type and body slots) at list index c: the bodies and accumulators
+// in registers, the pre-stepped terms read from LDS
+template <int K>
+MG_DEV Side vside_get(const RobotV &V) {
+    Side x = Side{};
+    x.vx = V.vx[K]; x.vy = V.vy[K]; x.w = V.w[K]; x.minv = V.minv[K]; x.iinv = V.iinv[K];
+    return x;
+}
+template <int K>
+MG_DEV void vside_put(RobotV &V, const Side &x) { V.vx[K] = x.vx; V.vy[K] = x.vy; V.w[K] = x.w; }
 template <int K>
 MG_DEV void rrow_apply(RobotV &V, const MGState &S, int e, int c, double dt) {
     constexpr ConsDesc d = static_cons(K);
-    constexpr int a = d.a, b = d.b;
-    if constexpr (d.type == MG_C_PIVOT) {
-        V2 r1 = v2(CPA(CP_R1X, c), CPA(CP_R1Y, c)), r2 = v2(CPA(CP_R2X, c), CPA(CP_R2Y, c));
-        V2 v1 = vadd(v2(V.vx[a], V.vy[a]), vmult(vperp(r1), V.w[a]));
-        V2 v2_ = vadd(v2(V.vx[b], V.vy[b]), vmult(vperp(r2), V.w[b]));
-        V2 vr = vsub(v2_, v1);
-        V2 dd = vsub(v2(CPA(CP_BIAS, c), CPA(CP_BIAS2, c)), vr);
-        V2 j = v2(dd.x * CPA(CP_K11, c) + dd.y * CPA(CP_K12, c), dd.x * CPA(CP_K21, c) + dd.y * CPA(CP_K22, c));
-        V2 jOld = v2(V.jacc[K], V.jacc2[K]);
-        V2 jAcc = vclamp(vadd(jOld, j), CPA(CP_MAXF, c) * dt);
-        V.jacc[K] = jAcc.x; V.jacc2[K] = jAcc.y;
-        V2 dj = vsub(jAcc, jOld);
-        const V2 ja = vneg(dj);
-        V.vx[a] = V.vx[a] + ja.x * V.minv[a]; V.vy[a] = V.vy[a] + ja.y * V.minv[a];
-        V.w[a] = V.w[a] + V.iinv[a] * vcross(r1, ja);
-        V.vx[b] = V.vx[b] + dj.x * V.minv[b]; V.vy[b] = V.vy[b] + dj.y * V.minv[b];
-        V.w[b] = V.w[b] + V.iinv[b] * vcross(r2, dj);
-    } else if constexpr (d.type == MG_C_GEAR) {
-        double ratio = CPA(CP_RATIO, c);
-        double wr = V.w[b] * ratio - V.w[a];
-        double jMax = CPA(CP_MAXF, c) * dt;
-        double j = (CPA(CP_BIAS, c) - wr) * CPA(CP_ISUM, c);
-        double jOld = V.jacc[K];
-        double jAcc = cpclamp(jOld + j, -jMax, jMax);
-        V.jacc[K] = jAcc;
-        j = jAcc - jOld;
-        V.w[a] = V.w[a] - j * V.iinv[a] * CPA(CP_RATIO_INV, c);
-        V.w[b] = V.w[b] + j * V.iinv[b];
-    } else if constexpr (d.type == MG_C_ROTLIMIT) {
-        double bias = CPA(CP_BIAS, c);
-        if (!bias) return;
-        double wr = V.w[b] - V.w[a];
-        double jMax = CPA(CP_MAXF, c) * dt;
-        double j = -(bias + wr) * CPA(CP_ISUM, c);
-        double jOld = V.jacc[K];
-        double jAcc = bias < 0.0 ? cpclamp(jOld + j, 0.0, jMax) : cpclamp(jOld + j, -jMax, 0.0);
-        V.jacc[K] = jAcc;
-        j = jAcc - jOld;
-        V.w[a] = V.w[a] - j * V.iinv[a];
-        V.w[b] = V.w[b] + j * V.iinv[b];
-    } else if constexpr (d.type == MG_C_MOTOR) {
-        double wr = V.w[b] - V.w[a] + CPA(CP_RATE, c);
-        double jMax = CPA(CP_MAXF, c) * dt;
-        double j = -wr * CPA(CP_ISUM, c);
-        double jOld = V.jacc[K];
-        double jAcc = cpclamp(jOld + j, -jMax, jMax);
-        V.jacc[K] = jAcc;
-        j = jAcc - jOld;
-        V.w[a] = V.w[a] - j * V.iinv[a];
-        V.w[b] = V.w[b] + j * V.iinv[b];
-    } else if constexpr (d.type == MG_C_SPRING) {
-        double wrn = V.w[a] - V.w[b];
-        double w_damp = (V.twrn[K] - wrn) * CPA(CP_WCOEF, c);
-        V.twrn[K] = wrn + w_damp;
-        double j_damp = w_damp * CPA(CP_ISUM, c);
-        V.jacc[K] = V.jacc[K] + j_damp;
-        V.w[a] = V.w[a] + j_damp * V.iinv[a];
-        V.w[b] = V.w[b] - j_damp * V.iinv[b];
-    }
+    RegCons q;
+    rc_load(q, S, e, c, d.type, dt);
+    Side A = vside_get<d.a>(V), B = vside_get<d.b>(V);
+    joint_row<true, true>(d.type, q, V.acc[K], A, B);
+    vside_put<d.a>(V, A);
+    vside_put<d.b>(V, B);
 }
 template <int K>
 MG_DEV void rrow_cached(RobotV &V, const MGState &S, int e, int c, double dt_coef) {
     constexpr ConsDesc d = static_cons(K);
-    constexpr int a = d.a, b = d.b;
-    if constexpr (d.type == MG_C_PIVOT) {
-        V2 j = vmult(v2(V.jacc[K], V.jacc2[K]), dt_coef);
-        const V2 r1 = v2(CPA(CP_R1X, c), CPA(CP_R1Y, c)), r2 = v2(CPA(CP_R2X, c), CPA(CP_R2Y, c));
-        const V2 ja = vneg(j);
-        V.vx[a] = V.vx[a] + ja.x * V.minv[a]; V.vy[a] = V.vy[a] + ja.y * V.minv[a];
-        V.w[a] = V.w[a] + V.iinv[a] * vcross(r1, ja);
-        V.vx[b] = V.vx[b] + j.x * V.minv[b]; V.vy[b] = V.vy[b] + j.y * V.minv[b];
-        V.w[b] = V.w[b] + V.iinv[b] * vcross(r2, j);
-    } else if constexpr (d.type == MG_C_GEAR) {
-        double j = V.jacc[K] * dt_coef;
-        V.w[a] = V.w[a] - j * V.iinv[a] * CPA(CP_RATIO_INV, c);
-        V.w[b] = V.w[b] + j * V.iinv[b];
-    } else if constexpr (d.type == MG_C_ROTLIMIT || d.type == MG_C_MOTOR) {
-        double j = V.jacc[K] * dt_coef;
-        V.w[a] = V.w[a] - j * V.iinv[a];
-        V.w[b] = V.w[b] + j * V.iinv[b];
-    }
+    RegCons q;
+    rc_load(q, S, e, c, d.type, 0.0);   // a warm start reads no jmax
+    Side A = vside_get<d.a>(V), B = vside_get<d.b>(V);
+    joint_cached<true, true>(d.type, q, V.acc[K], A, B, dt_coef);
+    vside_put<d.a>(V, A);
+    vside_put<d.b>(V, B);
 }
 template <int K = 0>
 MG_DEV void rrows_cached(RobotV &V, const MGState &S, int e, int rc0, double dt_coef) {
@@ -1749,11 +1378,7 @@ MG_DEV void space_step_coop(const MGState &S, const mg_library *L, double dt, in
             V.minv[k] = AT(S.bminv, b); V.iinv[k] = AT(S.biinv, b);
         }
 #pragma unroll
-        for (int k = 0; k < 10; k++) {
-            V.jacc[k] = CPA(CP_JACC, rc0 + k);
-            V.jacc2[k] = static_cons(k).type == MG_C_PIVOT ? CPA(CP_JACC2, rc0 + k) : 0.0;
-            V.twrn[k] = static_cons(k).type == MG_C_SPRING ? CPA(CP_TWRN, rc0 + k) : 0.0;
-        }
+        for (int k = 0; k < 10; k++) ra_load(V.acc[k], S, e, rc0 + k, static_cons(k).type);
         const int apk = lane < unact ? arb_pack(S, e, lane) : 0;   // active arbiter `lane` (arb_pack)
         for (int i = 0; i < unact; i++) xarb_row<true>(R, V, rb0, lane, S, e, __builtin_amdgcn_readlane(apk, i), dt_coef);
         if (G.n > 0) {
@@ -1782,11 +1407,7 @@ MG_DEV void space_step_coop(const MGState &S, const mg_library *L, double dt, in
         }
         if (lane == 0) {
 #pragma unroll
-            for (int k = 0; k < 10; k++) {
-                CPA(CP_JACC, rc0 + k) = V.jacc[k];
-                if (static_cons(k).type == MG_C_PIVOT) CPA(CP_JACC2, rc0 + k) = V.jacc2[k];
-                if (static_cons(k).type == MG_C_SPRING) CPA(CP_TWRN, rc0 + k) = V.twrn[k];
-            }
+            for (int k = 0; k < 10; k++) ra_store(V.acc[k], S, e, rc0 + k, static_cons(k).type);
         }
         MG_PP(P, 6);
         __syncthreads();

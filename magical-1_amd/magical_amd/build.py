@@ -18,7 +18,7 @@ OUT = os.path.join(HERE, "libmagical_sim.so")
 PROF_OUT = os.path.join(HERE, "libmagical_sim_prof.so")  # -DMG_PROFILE phase timers (tools/gpu_phase.py)
 _LAUNCH = ["mg_common.h", "mg_state.h", "mg_stepforms.h", "mg_launch.h"]
 _PHYS = _LAUNCH + ["mg_math.h", "mg_phys.h", "mg_prof.h"]
-_STEP = _PHYS + ["mg_step.h", "mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h", "mg_lanes.h"]
+_STEP = _PHYS + ["mg_step.h", "mg_rows.h", "mg_reset.h", "mg_score.h", "mg_stepk.h", "mg_stepq.h", "mg_lanes.h"]
 _LOOK = _STEP + ["mg_lookahead.h", "mg_rollout.h"]   # mg_lookahead's kernels: the step kernel's pairs with the env-step loop inside
 _SEQ = _STEP + ["mg_seq.h", "mg_rollout.h"]   # mg_step_seq's kernels: the same pairs, the loop on the live envs, mg_step's tail once
 _SIM = _LAUNCH + ["mg_sim.h", "mg_pool.h", "mg_plan.h", "mg_snapshot.h"]   # the units that hold a part of the C ABI
@@ -42,7 +42,7 @@ UNITS = {  # translation unit -> every header it includes, directly or not (one 
     "mg_seq_v4.hip": _SEQ,
     "mg_seq_quad.hip": _SEQ,
     "mg_seq_hbm.hip": _SEQ,
-    "mg_raster.hip": _PHYS + ["mg_step.h", "mg_render.h"],
+    "mg_raster.hip": _PHYS + ["mg_step.h", "mg_rows.h", "mg_render.h"],
     "mg_replay.hip": _SIM,
     "mg_scene.hip": _SIM + ["mg_math.h", "mg_phys.h", "mg_prof.h", "mg_reset.h", "mg_scene.h"],   # mg_get_scene, mg_reset_scene
 }
